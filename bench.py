@@ -7,13 +7,19 @@ evaluateGeneric: a full post-order traversal (48 newview CLV updates over
 all sites) + the root lnL evaluation + the per-partition lnL all-reduce
 (RCCL when world>1) — the per-partition body of SURVEY.md §3.1.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result
+line.  --dump-outputs DIR then also writes what the last timed step computed
+(DIR/lnl.npy, DIR/scalers.npy, DIR/clv_sample.npy).  --full adds the legs
+that take runs of their own: the roofline pass and the CPU baseline.
 
 N>1 is launched by the driver as one rank per GPU via torch.distributed.run;
 sites shard one-million-per-rank (weak scaling — per-GPU work fixed, the
 reference's site sharding with the C1 all-reduce in the loop).
 
-Output: ONE JSON line from rank 0 (see the repo contract), including
+Output: ONE JSON line from rank 0 (see the repo contract); with --full it
+also carries (null in a plain run)
   roofline     — the dominant kernel (newview INNER_INNER), algorithmic
                  bytes/launch over its HIP-event launch time vs 8 TB/s HBM3E
   cpu_baseline — the reference's own AVX kernel (oracle/_ref/libref.so)
@@ -109,6 +115,86 @@ def cpu_baseline_leg(width=200_000, budget_s=10.0, protein=False):
         return None
 
 
+def profile_pass(step, eng, steps):
+    """Roofline pass (--full): HIP-event per-launch timing of the same
+    kernels over a few extra steps (profiling bypasses the graph cache;
+    kernel durations are identical, only the launch gaps differ).  Returns
+    per-tipCase (ms, launch counts) and the number of profiled steps."""
+    L = ea.lib()
+    steps_prof = max(3, steps // 10)
+    L.examl_hip_profile_reset()
+    L.examl_hip_profile_enable(1)
+    for _ in range(steps_prof):
+        step()
+    eng.sync()
+    L.examl_hip_profile_enable(0)
+    ms = np.zeros(3)
+    cnt = np.zeros(3, dtype=np.int64)
+    L.examl_hip_profile_get(ms.ctypes.data_as(ctypes.c_void_p),
+                            cnt.ctypes.data_as(ctypes.c_void_p))
+    return ms, cnt, steps_prof
+
+
+def roofline_leg(ms, cnt, steps_prof, states, pw, P, tc_counts):
+    """The roofline dict.  P == 1: the dominant kernel (newview
+    INNER_INNER), bytes per launch over HIP-event launch time.  P > 1 (fused
+    mseg path): one launch covers many (op, partition) segments, so use
+    TOTAL algorithmic newview bytes over TOTAL newview kernel time for the
+    profiled steps — per-launch bytes would overcount."""
+    BPS_TC = {4: (130.0, 260.0, 388.0), 20: (164.0, 1124.0, 1924.0)}
+    bps = BYTES_PER_SITE_II[states]
+    ii_ms, ii_n = float(ms[2]), int(cnt[2])
+    if P == 1:
+        achieved = (bps * pw * ii_n) / (ii_ms * 1e-3) if ii_ms > 0 else None
+    else:
+        bytes_step = sum(tc_counts[t] * BPS_TC[states][t] * pw * P
+                         for t in range(3))
+        tot_ms = float(ms.sum())
+        achieved = (steps_prof * bytes_step) / (tot_ms * 1e-3) \
+            if tot_ms > 0 else None
+    # counter-measured HBM traffic for this exact workload, collected in a
+    # separate hardware-counter pass (see profiles/r01_pmc_traffic.json)
+    traffic = None
+    cal = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                       "profiles", "r01_pmc_traffic.json")
+    if pw == SITES_PER_GPU and states == 4 and os.path.exists(cal):
+        with open(cal) as f:
+            traffic = json.load(f)["traffic_bytes_per_launch"]
+    return {
+        "bound": "hbm",
+        "achieved": achieved / 1e9 if achieved else None,
+        "peak": HBM_PEAK / 1e9,
+        "unit": "GB/s",
+        "frac": achieved / HBM_PEAK if achieved else None,
+        "traffic": traffic,
+    }
+
+
+DUMP_CLV_BYTES = 32 << 20  # budget for the sampled CLV dump (64 MB cap)
+
+
+def dump_outputs(outdir, engines, lnl_t):
+    """Write what the last timed step left with its caller as float64 .npy:
+    the per-partition lnL, the per-node scaler counts and a fixed, seeded
+    site sample of every inner node's CLV (the full pool is GBs)."""
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "lnl.npy"),
+            lnl_t.detach().reshape(-1).cpu().numpy().astype(np.float64))
+    np.save(os.path.join(outdir, "scalers.npy"),
+            np.stack([e.d_scalers.cpu().numpy() for e in engines])
+            .astype(np.float64))
+    e0 = engines[0]
+    per_site = len(engines) * e0.ninner * e0.SPAN * 8
+    ns = max(1, min(e0.width, DUMP_CLV_BYTES // per_site))
+    idx = np.sort(np.random.default_rng(0).choice(e0.width, ns,
+                                                  replace=False))
+    d_idx = torch.from_numpy(idx).to(e0.device)
+    sample = np.stack([
+        e.d_clv.view(e.ninner, e.width, e.SPAN)[:, d_idx, :].cpu().numpy()
+        for e in engines])
+    np.save(os.path.join(outdir, "clv_sample.npy"), sample)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -126,6 +212,10 @@ def main():
                     help="FMA protein newview (the reference's _FMA build "
                          "class; ~1 ulp/op vs the bit-exact default)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/*.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the roofline pass and the CPU baseline")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -166,22 +256,25 @@ def main():
     n_ops = len(entries)
     tc_counts = [sum(1 for e in entries if e.tipCase == t) for t in range(3)]
 
+    last = {}
+
     def step():
         if P == 1:
             eng.newview_traversal(entries)
-            return eng.evaluate_root(tree, p, q, z, all_reduce=world > 1)
+            last["lnl"] = eng.evaluate_root(tree, p, q, z,
+                                            all_reduce=world > 1)
+            return last["lnl"]
         # partitioned: the fused mseg executors — one launch per
         # (traversal level x tipCase) covering all P partitions, then ONE
         # all-reduce of the per-partition lnL vector (the C1 collective)
         multi.newview_traversal(entries)
-        lnl_vec = multi.evaluate_root(tree, p, q, z, all_reduce=world > 1)
-        return lnl_vec.sum()
+        last["lnl"] = multi.evaluate_root(tree, p, q, z,
+                                          all_reduce=world > 1)
+        return last["lnl"].sum()
 
     # warmup (also captures the traversal's hipGraph)
     for _ in range(args.warmup):
-        lnl_t = step()
-    eng.sync()
-    lnl0 = float(lnl_t.sum().cpu())
+        step()
 
     # timed region: graph-replayed traversals, no profiling overhead
     if dist:
@@ -194,21 +287,13 @@ def main():
     if dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    lnl0 = float(last["lnl"].sum().cpu())
 
-    # roofline pass: HIP-event per-launch timing of the same kernels
-    # (profiling bypasses the graph cache; kernel durations are identical,
-    # only the launch gaps differ)
-    L = ea.lib()
-    L.examl_hip_profile_reset()
-    L.examl_hip_profile_enable(1)
-    for _ in range(max(3, args.steps // 10)):
-        step()
-    eng.sync()
-    L.examl_hip_profile_enable(0)
-    ms = np.zeros(3)
-    cnt = np.zeros(3, dtype=np.int64)
-    L.examl_hip_profile_get(ms.ctypes.data_as(ctypes.c_void_p),
-                            cnt.ctypes.data_as(ctypes.c_void_p))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, engines, last["lnl"])
+
+    if args.full:
+        ms, cnt, steps_prof = profile_pass(step, eng, args.steps)
 
     # max over ranks
     if dist:
@@ -219,47 +304,14 @@ def main():
     if rank != 0:
         return
 
-    # roofline.  P == 1: the dominant kernel (newview INNER_INNER), bytes
-    # per launch over HIP-event launch time.  P > 1 (fused mseg path): one
-    # launch covers many (op, partition) segments, so use TOTAL algorithmic
-    # newview bytes over TOTAL newview kernel time for the profiled steps —
-    # per-launch bytes would overcount.
-    BPS_TC = {4: (130.0, 260.0, 388.0), 20: (164.0, 1124.0, 1924.0)}
-    bps = BYTES_PER_SITE_II[model.states]
-    ii_ms, ii_n = float(ms[2]), int(cnt[2])
-    if P == 1:
-        achieved = (bps * pw * ii_n) / (ii_ms * 1e-3) \
-            if ii_ms > 0 else None
-    else:
-        steps_prof = max(3, args.steps // 10)
-        bytes_step = sum(tc_counts[t] * BPS_TC[model.states][t] * pw * P
-                         for t in range(3))
-        tot_ms = float(ms.sum())
-        achieved = (steps_prof * bytes_step) / (tot_ms * 1e-3) \
-            if tot_ms > 0 else None
-    # PMC-measured HBM traffic for this exact workload (collected in a
-    # separate rocprofv3 --pmc pass, corrected per MI355X_MICROARCH.md §HBM;
-    # see profiles/r01_pmc_traffic.json)
-    traffic = None
-    cal = os.path.join(os.path.dirname(os.path.abspath(__file__)),
-                       "profiles", "r01_pmc_traffic.json")
-    if pw == SITES_PER_GPU and model.states == 4 and os.path.exists(cal):
-        with open(cal) as f:
-            traffic = json.load(f)["traffic_bytes_per_launch"]
-    roofline = {
-        "bound": "hbm",
-        "achieved": achieved / 1e9 if achieved else None,
-        "peak": HBM_PEAK / 1e9,
-        "unit": "GB/s",
-        "frac": achieved / HBM_PEAK if achieved else None,
-        "traffic": traffic,
-    }
-
-    cpu = None
-    if not args.no_cpu_baseline and world == 1 \
-            and not os.environ.get("EXAML_BENCH_NO_CPU"):
-        log("timing CPU baseline (reference AVX kernel, 1 core)...")
-        cpu = cpu_baseline_leg(protein=args.protein)
+    roofline = cpu = None
+    if args.full:
+        roofline = roofline_leg(ms, cnt, steps_prof, model.states, pw, P,
+                                tc_counts)
+        if not args.no_cpu_baseline and world == 1 \
+                and not os.environ.get("EXAML_BENCH_NO_CPU"):
+            log("timing CPU baseline (reference AVX kernel, 1 core)...")
+            cpu = cpu_baseline_leg(protein=args.protein)
 
     site_updates = float(args.steps) * n_ops * width * world
     value = site_updates / elapsed

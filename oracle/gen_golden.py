@@ -16,6 +16,23 @@ sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 import oracle as O  # noqa: E402
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "..", "tests", "golden")
+PART_BYTES = 900_000  # random fp64 does not compress: keep each part small
+
+
+def save_parts(stem, arrays):
+    """Write `arrays` as GOLDEN/<stem>.<k>.npz, filling each part up to
+    PART_BYTES of raw data in insertion order (read back merged by
+    tests.helpers.load_golden_parts)."""
+    parts, size = [{}], 0
+    for k, v in arrays.items():
+        nb = np.asarray(v).nbytes
+        if parts[-1] and size + nb > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = v
+        size += nb
+    for i, part in enumerate(parts):
+        np.savez_compressed(os.path.join(GOLDEN, f"{stem}.{i}.npz"), **part)
 
 
 def main():
@@ -117,8 +134,7 @@ def main():
     cases["right"] = right
     cases["diag"] = diag
     cases["model"] = np.bytes_(name.encode())
-    np.savez_compressed(os.path.join(GOLDEN, "kernels_dna_gamma.npz"),
-                        **cases)
+    save_parts("kernels_dna_gamma", cases)
 
     # ---- protein (LG+GAMMA) ----------------------------------------------
     lg = np.load(os.path.join(os.path.dirname(__file__), "..", "examl_amd",
@@ -176,7 +192,7 @@ def main():
         d1, d2 = O.core_prot_gamma(n, st, EIGN, g, lz, wgt, lib=ref)
         pc[f"core_tc{tc}_d1"] = np.float64(d1)
         pc[f"core_tc{tc}_d2"] = np.float64(d2)
-    np.savez_compressed(os.path.join(GOLDEN, "kernels_prot_gamma.npz"), **pc)
+    save_parts("kernels_prot_gamma", pc)
     print("golden fixtures written to", GOLDEN)
 
 

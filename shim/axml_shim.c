@@ -24,7 +24,7 @@
  *
  * Build: shim/Makefile (compiles the reference's own L3/L4 TUs in place
  * from /root/reference — never copied — and links them against this TU +
- * libexaml_hip.so into shim/_build/examl-HIP).
+ * libexaml_hip.so into oracle/_ref/examl-HIP).
  * ==========================================================================*/
 
 #define __HIP_PLATFORM_AMD__ 1

@@ -2,12 +2,28 @@
 replays a product traversal on the CPU restatement (the checker for GPU
 parity and host-logic tests)."""
 
+import glob
 import math
+import os
 
 import numpy as np
 
 import oracle as O
 from examl_amd import INNER_INNER, TIP_INNER, TIP_TIP
+
+
+def load_golden_parts(golden_dir, stem):
+    """Merge the arrays of tests/golden/<stem>.<k>.npz (a fixture set that
+    oracle/gen_golden.py stores in parts to keep every file small)."""
+    paths = sorted(glob.glob(os.path.join(golden_dir, stem + ".*.npz")))
+    assert paths, f"no golden parts for {stem} in {golden_dir}"
+    out = {}
+    for path in paths:
+        with np.load(path) as d:
+            for k in d.files:
+                assert k not in out, f"{k} stored twice in {stem}"
+                out[k] = d[k]
+    return out
 
 
 def make_synthetic(ntips, width, seed=42):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import examl_amd as ea
+from tests.helpers import load_golden_parts
 
 HDR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                    "include", "examl_hip.h")
@@ -42,7 +43,7 @@ def test_product_model_prep_matches_golden(golden_dir):
 
 def test_product_make_p_and_diag_match_golden(golden_dir):
     d = np.load(os.path.join(golden_dir, "model_dna.npz"))
-    k = np.load(os.path.join(golden_dir, "kernels_dna_gamma.npz"))
+    k = load_golden_parts(golden_dir, "kernels_dna_gamma")
     m = ea.DnaGtrModel(d["m1_freqs"], d["m1_rates6"], float(d["m1_alpha"]))
     left = np.zeros(64)
     right = np.zeros(64)

@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 import examl_amd as ea
-from tests.helpers import make_synthetic, oracle_full_lnl, oracle_makenewz
+from tests.helpers import (load_golden_parts, make_synthetic, oracle_full_lnl,
+                           oracle_makenewz)
 
 torch = pytest.importorskip("torch")
 
@@ -29,7 +30,7 @@ def dev():
 
 @pytest.fixture(scope="module")
 def kern(golden_dir):
-    return np.load(os.path.join(golden_dir, "kernels_dna_gamma.npz"))
+    return load_golden_parts(golden_dir, "kernels_dna_gamma")
 
 
 @pytest.fixture(scope="module")

@@ -9,7 +9,8 @@ import numpy as np
 import pytest
 
 import examl_amd as ea
-from tests.helpers import make_synthetic_aa, oracle_full_lnl, oracle_makenewz
+from tests.helpers import (load_golden_parts, make_synthetic_aa,
+                           oracle_full_lnl, oracle_makenewz)
 
 torch = pytest.importorskip("torch")
 
@@ -28,7 +29,7 @@ def dev():
 
 @pytest.fixture(scope="module")
 def kern(golden_dir):
-    return np.load(os.path.join(golden_dir, "kernels_prot_gamma.npz"))
+    return load_golden_parts(golden_dir, "kernels_prot_gamma")
 
 
 def _to_dev(a, dev):

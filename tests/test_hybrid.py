@@ -1,7 +1,7 @@
 """The literal C drop-in (SURVEY §8b / VERDICT r01 #1): the UNMODIFIED
 reference search (searchAlgo.c/optimizeModel.c/axml.c compiled in place
 from /root/reference) linked against libexaml_hip.so through
-shim/axml_shim.c.  The hybrid binary shim/_build/examl-HIP is prebuilt by
+shim/axml_shim.c.  The hybrid binary oracle/_ref/examl-HIP is prebuilt by
 __graft_entry__.build() in the dev container and travels to the GPU box
 with the snapshot; nothing here reads /root/reference at run time.
 
@@ -17,7 +17,7 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
-HYBRID = os.path.join(REPO, "shim", "_build", "examl-HIP")
+HYBRID = os.path.join(REPO, "oracle", "_ref", "examl-HIP")
 GOLDEN = os.path.join(HERE, "golden")
 
 GOLDEN_F_E = -16205.671990   # reference -f E on testData/49

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import oracle as O
+from tests.helpers import load_golden_parts
 
 
 @pytest.fixture(scope="module")
@@ -20,7 +21,7 @@ def model(golden_dir):
 
 @pytest.fixture(scope="module")
 def kern(golden_dir):
-    return np.load(os.path.join(golden_dir, "kernels_dna_gamma.npz"))
+    return load_golden_parts(golden_dir, "kernels_dna_gamma")
 
 
 def _aligned_copy(a):

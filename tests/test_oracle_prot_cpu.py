@@ -7,11 +7,12 @@ import numpy as np
 import pytest
 
 import oracle as O
+from tests.helpers import load_golden_parts
 
 
 @pytest.fixture(scope="module")
 def kern(golden_dir):
-    return np.load(os.path.join(golden_dir, "kernels_prot_gamma.npz"))
+    return load_golden_parts(golden_dir, "kernels_prot_gamma")
 
 
 def _al(a):
