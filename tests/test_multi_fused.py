@@ -59,6 +59,34 @@ def test_full_lnl_matches_per_partition(states):
 
 
 @pytest.mark.parametrize("states", [4, 20])
+def test_full_lnl_under_rescaling_ragged_widths(states):
+    """The mseg kernels carry their own copy of the 2^-256 rescale vote:
+    ragged partition widths (one of them a single site) on a caterpillar
+    deep enough that CLVs rescale.  Scalers are not compared — fused P
+    matrices differ from the host's in the last ulps, so a site sitting on
+    the threshold may scale on one side only; lnL absorbs that through the
+    undo term."""
+    from tests.helpers import deep_caterpillar, fused_deep_inputs
+    ntips, parts = fused_deep_inputs(states)
+    engines = [ea.DnaGammaEngine(t, w, m, device="cuda:0")
+               for t, w, m in parts]
+    multi = ea.MultiDnaEngine(engines)
+    tree = deep_caterpillar(ntips)
+    entries, (p, q, z) = tree.full_traversal()
+    single, sc_single = [], []
+    for e in engines:
+        e.newview_traversal(entries)
+        single.append(float(e.evaluate_root(tree, p, q, z).cpu()))
+        sc_single.append(int(e.d_scalers.max().item()))
+        e.d_scalers.zero_()   # the fused path shares these buffers
+    vec = multi.full_lnl(tree).cpu().numpy()
+    sc_fused = [int(e.d_scalers.max().item()) for e in engines]
+    assert max(sc_single) > 0 and max(sc_fused) > 0, (sc_single, sc_fused)
+    for s, f in zip(single, vec):
+        assert abs(f - s) <= 1e-11 * abs(s), (s, f)
+
+
+@pytest.mark.parametrize("states", [4, 20])
 def test_masked_partitions_stay_stale(states):
     engines, multi, tree = _mk(states=states)
     entries, (p, q, z) = tree.full_traversal()
