@@ -147,6 +147,12 @@ def _bind(lib):
         [p, i, i, i, d, l, d, i, p, p, p, p, p, l, i]
     lib.examl_hip_use_graphs.argtypes = [i]
     lib.examl_hip_graphs_clear.argtypes = []
+    lib.examl_hip_use_fused.argtypes = [i]
+    lib.examl_hip_fused_plan.argtypes = [p, i, i, p, p, p]
+    lib.examl_hip_fused_depth.argtypes = []
+    lib.examl_hip_fused_max_ops.argtypes = []
+    lib.examl_hip_fused_grid_cap.argtypes = []
+    lib.examl_hip_fused_tile_sites.argtypes = []
     lib.examl_hip_fast_math.argtypes = [i]
     # -S prot GAMMA + CAT families
     lib.examl_host_make_p_save.argtypes = [d, d, p, p, p, i, p, p, i, i]

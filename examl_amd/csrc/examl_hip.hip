@@ -180,6 +180,297 @@ __global__ __launch_bounds__(NV_BLOCK) void k_newview_dna_gamma(
   }
 }
 
+/* --- fused newview traversal -----------------------------------------------
+ * Runs a whole run of traversal entries per 128-site tile so that a child
+ * CLV produced by this thread is handed to its parent on chip instead of
+ * being read back from HBM (every x3 is still stored: the pool stays
+ * complete for later partial traversals and the root kernels).
+ *
+ * The host planner (fused_plan, below) resolves every inner operand to one
+ * of three sources, all block-uniform:
+ *   MEM  the CLV pool — written before this launch, never by it;
+ *   REG  the quartet the previous op of this launch left in registers;
+ *   LDS  a per-thread operand-stack slot (sStk[slot][unit][.][tid], touched
+ *        by its own thread only, so the stack needs no barrier).
+ * A thread owns FUSED_U (site, cat) units of a tile, NV_BLOCK units apart,
+ * so every wave access stays 2 KiB contiguous; two units per thread halve
+ * the staging and barriers per byte stored (A/B log: DESIGN.md).
+ * Math, summation order, rescale vote and stores restate
+ * k_newview_dna_gamma expression by expression (bit-identical results).
+ *
+ * Barrier rules: the P block and the ump tables of op k+1 are staged into
+ * the other half of a double buffer while op k computes, with ONE
+ * __syncthreads per op.  Every thread of the block reaches that barrier on
+ * every op of every tile: the tile loop depends on blockIdx/gridDim only,
+ * the op loop on prog.count only, and threads of the ragged last tile are
+ * predicated off (`active`) for loads, stores and atomics — there is no
+ * return/continue/break inside the loops.  Tiles and a thread's units start
+ * at multiples of 256 units, so the 4-lane ballot groups of a site are
+ * always whole.
+ */
+#ifndef FUSED_D
+#define FUSED_D 4          /* on-chip operand-stack slots */
+#endif
+#ifndef FUSED_GRID_CAP
+#define FUSED_GRID_CAP 4096 /* blocks per launch; they stride over tiles */
+#endif
+#define FUSED_MAX_OPS 192  /* ops per launch (program travels by value) */
+#ifndef FUSED_U
+#define FUSED_U 2          /* (site, cat) units per thread and tile */
+#endif
+#define FUSED_UNITS (FUSED_U * NV_BLOCK)   /* units per tile */
+#define FUSED_SITES (FUSED_UNITS / 4)      /* sites per tile (4 cats) */
+
+#define FSRC_MEM 0u
+#define FSRC_REG 1u
+#define FSRC_LDS 2u
+
+struct FusedProg {
+  int x1[FUSED_MAX_OPS], x2[FUSED_MAX_OPS], x3[FUSED_MAX_OPS];
+  /* ctl: [1:0] tipCase  [3:2] x1 source  [5:4] x2 source
+   *      [9:6] x1 stack slot  [13:10] x2 stack slot
+   *      [14] keep x3 in stack slot [19:16] */
+  unsigned int ctl[FUSED_MAX_OPS];
+  int count; /* ops in this launch */
+  int base;  /* index of the first one in the call (P block, scalerInc) */
+};
+
+template <bool NT>
+__global__ __launch_bounds__(NV_BLOCK) void k_newview_dna_gamma_fused(
+    const FusedProg prog, double *__restrict__ clv, long clvStride,
+    const unsigned char *__restrict__ tips, long tipStride,
+    const double *__restrict__ pbuf, const double *__restrict__ EV,
+    const double *__restrict__ tipVec, const int *__restrict__ wgt, long n,
+    unsigned int *__restrict__ scalerInc) {
+  __shared__ double sEV[16], sTV[64];
+  __shared__ double sP[2][128], sU1[2][256], sU2[2][256];
+  __shared__ v2d sStk[FUSED_D][FUSED_U][2][NV_BLOCK];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int cat = tid & 3;
+  const int count = prog.count;
+  const long tiles = (n + FUSED_SITES - 1) / FUSED_SITES;
+
+  if (tid < 64) sTV[tid] = tipVec[tid];
+  if (tid < 16) sEV[tid] = EV[tid];
+  __syncthreads();
+
+  /* ump-table coordinates of this thread (k_newview_dna_gamma's) */
+  const int ucode = tid >> 4, ucat = (tid >> 2) & 3, urow = tid & 3;
+  const double tv0 = sTV[ucode * 4 + 0], tv1 = sTV[ucode * 4 + 1],
+               tv2 = sTV[ucode * 4 + 2], tv3 = sTV[ucode * 4 + 3];
+  const int uoff = ucat * 16 + urow * 4;
+
+  /* stage op 0 into buffer 0 */
+  {
+    const double *P = pbuf + (long)prog.base * 128;
+    const int tc0 = (int)(prog.ctl[0] & 3u);
+    if (tid < 128) sP[0][tid] = P[tid];
+    if (tc0 != EXAML_INNER_INNER) {
+      const double *pl = &P[uoff];
+      sU1[0][tid] = (pl[0] * tv0 + pl[1] * tv1) + (pl[2] * tv2 + pl[3] * tv3);
+      if (tc0 == EXAML_TIP_TIP) {
+        const double *pr = &P[64 + uoff];
+        sU2[0][tid] =
+            (pr[0] * tv0 + pr[1] * tv1) + (pr[2] * tv2 + pr[3] * tv3);
+      }
+    }
+  }
+
+  /* tip codes of the first op of the first tile; a thread owns FUSED_U
+   * units of a tile, NV_BLOCK units apart */
+  int c1[FUSED_U], c2[FUSED_U];
+  {
+    const int tc0 = (int)(prog.ctl[0] & 3u);
+#pragma unroll
+    for (int u = 0; u < FUSED_U; u++) {
+      const long site0 =
+          ((long)blockIdx.x * FUSED_UNITS + u * NV_BLOCK + tid) >> 2;
+      c1[u] = c2[u] = 0;
+      if (tc0 != EXAML_INNER_INNER && site0 < n)
+        c1[u] = tips[(long)prog.x1[0] * tipStride + site0];
+      if (tc0 == EXAML_TIP_TIP && site0 < n)
+        c2[u] = tips[(long)prog.x2[0] * tipStride + site0];
+    }
+  }
+  __syncthreads();
+
+  int buf = 0;
+  double r[FUSED_U][4]; /* previous op's quartets (REG) */
+#pragma unroll
+  for (int u = 0; u < FUSED_U; u++) r[u][0] = r[u][1] = r[u][2] = r[u][3] = 0;
+
+  for (long t = blockIdx.x; t < tiles; t += gridDim.x) {
+    for (int e = 0; e < count; e++) {
+      const unsigned int ctl = prog.ctl[e];
+      const int tc = (int)(ctl & 3u);
+
+      /* ---- prefetch the next op's staging inputs and tip codes (the op
+       * after the last one is op 0 of this block's next tile; past the
+       * last tile every lane is inactive and the staged data is unused) */
+      const int en = (e + 1 == count) ? 0 : e + 1;
+      const long tn = (e + 1 == count) ? t + gridDim.x : t;
+      const int tcn = (int)(prog.ctl[en] & 3u);
+      const double *Pn = pbuf + (long)(prog.base + en) * 128;
+      double pn = 0, pl0 = 0, pl1 = 0, pl2 = 0, pl3 = 0, pr0 = 0, pr1 = 0,
+             pr2 = 0, pr3 = 0;
+      int c1n[FUSED_U], c2n[FUSED_U];
+      if (tid < 128) pn = Pn[tid];
+      if (tcn != EXAML_INNER_INNER) {
+        pl0 = Pn[uoff + 0];
+        pl1 = Pn[uoff + 1];
+        pl2 = Pn[uoff + 2];
+        pl3 = Pn[uoff + 3];
+        if (tcn == EXAML_TIP_TIP) {
+          pr0 = Pn[64 + uoff + 0];
+          pr1 = Pn[64 + uoff + 1];
+          pr2 = Pn[64 + uoff + 2];
+          pr3 = Pn[64 + uoff + 3];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < FUSED_U; u++) {
+        const long siten = (tn * FUSED_UNITS + u * NV_BLOCK + tid) >> 2;
+        c1n[u] = c2n[u] = 0;
+        if (tcn != EXAML_INNER_INNER && siten < n)
+          c1n[u] = tips[(long)prog.x1[en] * tipStride + siten];
+        if (tcn == EXAML_TIP_TIP && siten < n)
+          c2n[u] = tips[(long)prog.x2[en] * tipStride + siten];
+      }
+
+      /* ---- op e on this tile ---- */
+      const double *sL = sP[buf], *sR = sP[buf] + 64;
+#pragma unroll
+      for (int u = 0; u < FUSED_U; u++) {
+        const long idx = t * FUSED_UNITS + u * NV_BLOCK + tid;
+        const long site = idx >> 2;
+        const bool active = site < n;
+        double u1[4], u2[4];
+        if (tc == EXAML_TIP_TIP) {
+#pragma unroll
+          for (int l = 0; l < 4; l++) {
+            u1[l] = sU1[buf][c1[u] * 16 + cat * 4 + l];
+            u2[l] = sU2[buf][c2[u] * 16 + cat * 4 + l];
+          }
+        } else {
+          /* x2 is an inner operand in both remaining cases */
+          double xr0, xr1, xr2, xr3;
+          const unsigned int k2 = (ctl >> 4) & 3u;
+          if (k2 == FSRC_REG) {
+            xr0 = r[u][0]; xr1 = r[u][1]; xr2 = r[u][2]; xr3 = r[u][3];
+          } else if (k2 == FSRC_LDS) {
+            const int sl = (int)((ctl >> 10) & 15u);
+            const v2d lo = sStk[sl][u][0][tid], hi = sStk[sl][u][1][tid];
+            xr0 = lo.x; xr1 = lo.y; xr2 = hi.x; xr3 = hi.y;
+          } else {
+            double4 v = make_double4(0, 0, 0, 0);
+            if (active)
+              v = *reinterpret_cast<const double4 *>(
+                  &clv[(long)prog.x2[e] * clvStride + idx * 4]);
+            xr0 = v.x; xr1 = v.y; xr2 = v.z; xr3 = v.w;
+          }
+          if (tc == EXAML_INNER_INNER) {
+            double xl0, xl1, xl2, xl3;
+            const unsigned int k1 = (ctl >> 2) & 3u;
+            if (k1 == FSRC_REG) {
+              xl0 = r[u][0]; xl1 = r[u][1]; xl2 = r[u][2]; xl3 = r[u][3];
+            } else if (k1 == FSRC_LDS) {
+              const int sl = (int)((ctl >> 6) & 15u);
+              const v2d lo = sStk[sl][u][0][tid], hi = sStk[sl][u][1][tid];
+              xl0 = lo.x; xl1 = lo.y; xl2 = hi.x; xl3 = hi.y;
+            } else {
+              double4 v = make_double4(0, 0, 0, 0);
+              if (active)
+                v = *reinterpret_cast<const double4 *>(
+                    &clv[(long)prog.x1[e] * clvStride + idx * 4]);
+              xl0 = v.x; xl1 = v.y; xl2 = v.z; xl3 = v.w;
+            }
+#pragma unroll
+            for (int l = 0; l < 4; l++) {
+              const double *pl = &sL[cat * 16 + l * 4];
+              const double *pr = &sR[cat * 16 + l * 4];
+              u1[l] =
+                  (xl0 * pl[0] + xl1 * pl[1]) + (xl2 * pl[2] + xl3 * pl[3]);
+              u2[l] =
+                  (xr0 * pr[0] + xr1 * pr[1]) + (xr2 * pr[2] + xr3 * pr[3]);
+            }
+          } else {
+#pragma unroll
+            for (int l = 0; l < 4; l++) {
+              const double *pr = &sR[cat * 16 + l * 4];
+              u1[l] = sU1[buf][c1[u] * 16 + cat * 4 + l];
+              u2[l] =
+                  (xr0 * pr[0] + xr1 * pr[1]) + (xr2 * pr[2] + xr3 * pr[3]);
+            }
+          }
+        }
+
+        double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+#pragma unroll
+        for (int l = 0; l < 4; l++) {
+          const double tt = u1[l] * u2[l];
+          a0 += tt * sEV[l * 4 + 0];
+          a1 += tt * sEV[l * 4 + 1];
+          a2 += tt * sEV[l * 4 + 2];
+          a3 += tt * sEV[l * 4 + 3];
+        }
+
+        if (tc != EXAML_TIP_TIP) {
+          /* site-wide rescale vote over the site's 4 lanes; inactive lanes
+           * vote "not small" and come in whole groups of 4 */
+          const bool small = active & (fabs(a0) < MINLIKELIHOOD) &
+                             (fabs(a1) < MINLIKELIHOOD) &
+                             (fabs(a2) < MINLIKELIHOOD) &
+                             (fabs(a3) < MINLIKELIHOOD);
+          const unsigned long long m = __ballot(small);
+          if (((m >> (lane & ~3)) & 0xFULL) == 0xFULL) {
+            a0 *= TWOTOTHE256;
+            a1 *= TWOTOTHE256;
+            a2 *= TWOTOTHE256;
+            a3 *= TWOTOTHE256;
+            if ((lane & 3) == 0)
+              atomicAdd(scalerInc + prog.base + e, (unsigned int)wgt[site]);
+          }
+        }
+
+        if (active) {
+          double *x3 = &clv[(long)prog.x3[e] * clvStride + idx * 4];
+          if (NT)
+            __builtin_nontemporal_store((v4d){a0, a1, a2, a3},
+                                        reinterpret_cast<v4d *>(x3));
+          else
+            *reinterpret_cast<double4 *>(x3) = make_double4(a0, a1, a2, a3);
+        }
+        if (ctl & (1u << 14)) {
+          const int sl = (int)((ctl >> 16) & 15u);
+          sStk[sl][u][0][tid] = (v2d){a0, a1};
+          sStk[sl][u][1][tid] = (v2d){a2, a3};
+        }
+        r[u][0] = a0; r[u][1] = a1; r[u][2] = a2; r[u][3] = a3;
+      }
+
+      /* ---- write the next op's staging into the other buffer (last read
+       * by op e-1, which every thread finished before the previous
+       * barrier) ---- */
+      const int nb = buf ^ 1;
+      if (tid < 128) sP[nb][tid] = pn;
+      if (tcn != EXAML_INNER_INNER) {
+        sU1[nb][tid] = (pl0 * tv0 + pl1 * tv1) + (pl2 * tv2 + pl3 * tv3);
+        if (tcn == EXAML_TIP_TIP)
+          sU2[nb][tid] = (pr0 * tv0 + pr1 * tv1) + (pr2 * tv2 + pr3 * tv3);
+      }
+#pragma unroll
+      for (int u = 0; u < FUSED_U; u++) {
+        c1[u] = c1n[u];
+        c2[u] = c2n[u];
+      }
+      __syncthreads();
+      buf = nb;
+    }
+  }
+}
+
 /* --- evaluate --------------------------------------------------------------
  * Restates evaluateGTRGAMMA (evaluateGenericSpecial.c:1879):
  *   term_i = sum_{c,k} x1[i,c,k]*x2[i,c,k]*diag[c,k]
@@ -1417,10 +1708,13 @@ struct TravGraph {
 static thread_local std::vector<TravGraph> g_graphs;
 static bool g_use_graphs = true;
 static bool g_fast_math = false;
+static bool g_use_fused = true;
 
 extern "C" void examl_hip_fast_math(int on) { g_fast_math = on != 0; }
 
 extern "C" void examl_hip_use_graphs(int on) { g_use_graphs = on != 0; }
+
+extern "C" void examl_hip_use_fused(int on) { g_use_fused = on != 0; }
 
 extern "C" void examl_hip_graphs_clear(void) {
   for (auto &g : g_graphs) hipGraphExecDestroy(g.exec);
@@ -1452,6 +1746,7 @@ static unsigned long long trav_key(const examl_hip_trav_entry *ops,
   mix((unsigned long long)(uintptr_t)stream);
   mix((unsigned long long)states);
   mix((unsigned long long)(g_fast_math ? 1 : 0));
+  mix((unsigned long long)(g_use_fused ? 1 : 0));
   for (int e = 0; e < numOps; e++) {
     mix(((unsigned long long)ops[e].tipCase << 48) ^
         ((unsigned long long)(unsigned)ops[e].pNumber << 32) ^
@@ -1522,6 +1817,187 @@ static HostPSlot *hostP_get(const void *dev_pbuf, size_t doubles) {
   return slot;
 }
 
+/* --- fused-traversal launch planner (host only, no GPU call) ---------------
+ * Cuts an entry list into launches of k_newview_dna_gamma_fused and
+ * resolves every inner operand to "on chip" or "CLV pool".
+ *
+ * Entries in reference order (computeTraversalInfo: q-subtree, r-subtree,
+ * then p) use their inner operands like a stack: TIP_TIP pushes, TIP_INNER
+ * replaces the top, INNER_INNER pops two (x2 on top, x1 below) and pushes
+ * one.  The planner simulates that stack with capacity maxDepth.  Stack
+ * position h lives in slot h % maxDepth; a push beyond the capacity
+ * overwrites (evicts) the bottom entry, which costs nothing because every
+ * x3 is stored to the pool anyway.
+ *
+ * Invariant: an operand is taken on chip only if the same launch produced
+ * it; anything read from the pool was written before the launch started
+ * (by an earlier launch in stream order, or before the call).  So:
+ *   - an operand no earlier op of this call produced is MEM;
+ *   - an operand an EARLIER launch of this call produced is MEM;
+ *   - an operand the CURRENT launch produced must be exactly where stack
+ *     order puts it (x2 on top, x1 below; a lone on-chip operand on top).
+ *     If it is not — evicted, buried, or out of order — a new launch
+ *     starts at this op with an empty stack, which makes it MEM.
+ * A launch also ends when it holds max_ops ops (one kernel-argument
+ * struct).
+ */
+struct FusedPlanOp {
+  int launch;       /* launch index of this op */
+  int s1, s2;       /* -1 = MEM, else on-chip slot of x1 / x2 */
+  int p1, p2;       /* producing op of an on-chip operand (else -1) */
+  int dst;          /* slot the result occupies */
+};
+
+static int fused_plan(const examl_hip_trav_entry *ops, int numOps,
+                      int maxDepth, int max_ops,
+                      std::vector<FusedPlanOp> &out) {
+  out.clear();
+  if (numOps < 0 || maxDepth < 1 || maxDepth > 16 || max_ops < 1) return -1;
+  struct Ent { int op, clv; };
+  std::vector<Ent> ring((size_t)maxDepth);
+  long bottom = 0, top = 0; /* live stack positions [bottom, top) */
+  int launch = 0, in_launch = 0, launch_start = 0;
+  /* last op of this call that produced a CLV slot (linear probe over the
+   * ops seen so far is O(n^2); a small open hash keeps it linear) */
+  size_t cap = 16;
+  while (cap < (size_t)numOps * 2 + 2) cap <<= 1;
+  std::vector<int> hkey(cap, -1), hval(cap, -1);
+  auto h_find = [&](int clv) -> int {
+    size_t i = ((size_t)(unsigned)clv * 2654435761u) & (cap - 1);
+    while (hkey[i] != -1) {
+      if (hkey[i] == clv) return hval[i];
+      i = (i + 1) & (cap - 1);
+    }
+    return -1;
+  };
+  auto h_put = [&](int clv, int op) {
+    size_t i = ((size_t)(unsigned)clv * 2654435761u) & (cap - 1);
+    while (hkey[i] != -1 && hkey[i] != clv) i = (i + 1) & (cap - 1);
+    hkey[i] = clv;
+    hval[i] = op;
+  };
+
+  for (int e = 0; e < numOps; e++) {
+    const examl_hip_trav_entry &op = ops[e];
+    if (op.tipCase != EXAML_TIP_TIP && op.tipCase != EXAML_TIP_INNER &&
+        op.tipCase != EXAML_INNER_INNER)
+      return -1;
+    if (op.x3Slot < 0) return -1;
+    if (in_launch == max_ops) {
+      launch++;
+      launch_start = e;
+      in_launch = 0;
+      bottom = top = 0;
+    }
+    /* inner operands, top of stack first */
+    int want[2], nwant = 0;
+    if (op.tipCase != EXAML_TIP_TIP) want[nwant++] = op.x2Slot;
+    if (op.tipCase == EXAML_INNER_INNER) want[nwant++] = op.x1Slot;
+
+    FusedPlanOp po;
+    for (int attempt = 0;; attempt++) {
+      po.launch = launch;
+      po.s1 = po.s2 = po.p1 = po.p2 = -1;
+      long t = top;
+      bool cut = false;
+      for (int k = 0; k < nwant; k++) {
+        const int prod = h_find(want[k]);
+        if (prod < launch_start) continue; /* not of this launch: MEM */
+        /* produced by this launch: must be the next entry down */
+        if (t > bottom && ring[(size_t)((t - 1) % maxDepth)].op == prod) {
+          t--;
+          const int slot = (int)(t % maxDepth);
+          if (k == 0 && op.tipCase != EXAML_TIP_TIP) {
+            po.s2 = slot;
+            po.p2 = prod;
+          } else {
+            po.s1 = slot;
+            po.p1 = prod;
+          }
+        } else {
+          cut = true;
+          break;
+        }
+      }
+      if (!cut) {
+        top = t;
+        break;
+      }
+      /* a fresh launch resolves every operand to MEM: one retry ends it */
+      if (attempt > 0) return -1;
+      launch++;
+      launch_start = e;
+      in_launch = 0;
+      bottom = top = 0;
+    }
+    /* push the result */
+    po.dst = (int)(top % maxDepth);
+    ring[(size_t)po.dst] = {e, op.x3Slot};
+    top++;
+    if (top - bottom > maxDepth) bottom++;
+    h_put(op.x3Slot, e);
+    in_launch++;
+    out.push_back(po);
+  }
+  return numOps > 0 ? launch + 1 : 0;
+}
+
+extern "C" int examl_hip_fused_plan(const examl_hip_trav_entry *ops,
+                                    int numOps, int maxDepth,
+                                    int *launch_of_op, int *src1, int *src2) {
+  std::vector<FusedPlanOp> plan;
+  const int nl = fused_plan(ops, numOps, maxDepth, FUSED_MAX_OPS, plan);
+  if (nl < 0) return nl;
+  for (int e = 0; e < numOps; e++) {
+    launch_of_op[e] = plan[(size_t)e].launch;
+    src1[e] = plan[(size_t)e].s1;
+    src2[e] = plan[(size_t)e].s2;
+  }
+  return nl;
+}
+
+extern "C" int examl_hip_fused_depth(void) { return FUSED_D; }
+extern "C" int examl_hip_fused_max_ops(void) { return FUSED_MAX_OPS; }
+extern "C" int examl_hip_fused_grid_cap(void) { return FUSED_GRID_CAP; }
+extern "C" int examl_hip_fused_tile_sites(void) { return FUSED_SITES; }
+
+/* Kernel-argument program of the launch that starts at op `first` and
+ * holds `len` ops.  The top of the stack is always the previous op's
+ * result, so an on-chip operand produced by op e-1 comes from registers
+ * (REG) and only results consumed later than that are kept in LDS. */
+static void fused_build_prog(const examl_hip_trav_entry *ops,
+                             const std::vector<FusedPlanOp> &plan, int first,
+                             int len, FusedProg *pg) {
+  pg->count = len;
+  pg->base = first;
+  for (int i = 0; i < len; i++) {
+    const int e = first + i;
+    const FusedPlanOp &po = plan[(size_t)e];
+    unsigned int ctl = (unsigned int)ops[e].tipCase & 3u;
+    auto kind = [&](int slot, int prod) -> unsigned int {
+      if (slot < 0) return FSRC_MEM;
+      return prod == e - 1 ? FSRC_REG : FSRC_LDS;
+    };
+    ctl |= kind(po.s1, po.p1) << 2;
+    ctl |= kind(po.s2, po.p2) << 4;
+    ctl |= (unsigned int)(po.s1 < 0 ? 0 : po.s1) << 6;
+    ctl |= (unsigned int)(po.s2 < 0 ? 0 : po.s2) << 10;
+    ctl |= (unsigned int)po.dst << 16;
+    pg->ctl[i] = ctl;
+    pg->x1[i] = ops[e].x1Slot;
+    pg->x2[i] = ops[e].x2Slot;
+    pg->x3[i] = ops[e].x3Slot;
+  }
+  /* keep-in-LDS flags: a result read on chip by anything but the next op */
+  for (int i = 0; i < len; i++) {
+    const FusedPlanOp &po = plan[(size_t)(first + i)];
+    const int prods[2] = {po.p1, po.p2};
+    for (int k = 0; k < 2; k++)
+      if (prods[k] >= 0 && prods[k] != first + i - 1)
+        pg->ctl[prods[k] - first] |= 1u << 14;
+  }
+}
+
 /* --- batched traversal (newviewIterative body) --------------------------- */
 
 template <int STATES>
@@ -1588,8 +2064,45 @@ static int traversal_impl(const examl_hip_trav_entry *ops, int numOps,
      * (protein uses two lanes per (site,cat) -> 8 units per site) */
     const int grid = grid_for(n * (STATES == 4 ? 4 : 8));
     const bool nt = (STATES == 4) && (n >= 65536);
+    /* DNA: runs of >= 2 ops the planner accepts go through the fused
+     * kernel; single-op launches, rejected lists and the HIP-event
+     * profiling mode keep the per-op kernels below */
+    std::vector<FusedPlanOp> plan;
+    std::vector<int> fused_len((size_t)numOps, 0);
+    if (STATES == 4 && g_use_fused && !g_prof_on &&
+        fused_plan(ops, numOps, FUSED_D, FUSED_MAX_OPS, plan) > 0) {
+      for (int e = 0; e < numOps;) {
+        int len = 1;
+        while (e + len < numOps &&
+               plan[(size_t)(e + len)].launch == plan[(size_t)e].launch)
+          len++;
+        fused_len[(size_t)e] = len;
+        e += len;
+      }
+    }
     for (int e = 0; e < numOps && rc == 0; e++) {
       const examl_hip_trav_entry *op = &ops[e];
+      if (fused_len[(size_t)e] >= 2) {
+        FusedProg pg;
+        fused_build_prog(ops, plan, e, fused_len[(size_t)e], &pg);
+        const long tiles = (n + FUSED_SITES - 1) / FUSED_SITES;
+        const int fgrid =
+            (int)(tiles < FUSED_GRID_CAP ? tiles : FUSED_GRID_CAP);
+        if (nt)
+          hipLaunchKernelGGL((k_newview_dna_gamma_fused<true>), dim3(fgrid),
+                             dim3(NV_BLOCK), 0, s, pg, dev_clv, clvStride,
+                             dev_tips, tipStride, dev_pbuf, dev_EV,
+                             dev_tipVec, dev_wgt, n, dev_inc);
+        else
+          hipLaunchKernelGGL((k_newview_dna_gamma_fused<false>), dim3(fgrid),
+                             dim3(NV_BLOCK), 0, s, pg, dev_clv, clvStride,
+                             dev_tips, tipStride, dev_pbuf, dev_EV,
+                             dev_tipVec, dev_wgt, n, dev_inc);
+        err = hipGetLastError();
+        if (err != hipSuccess) { rc = set_err(err, "fused newview launch"); break; }
+        e += fused_len[(size_t)e] - 1;
+        continue;
+      }
       hipEvent_t ev_a = nullptr, ev_b = nullptr;
       if (g_prof_on) {
         prof_begin(&ev_a, &ev_b);

@@ -181,6 +181,38 @@ int examl_hip_newview_traversal_dna_gamma(
     long n, unsigned int *dev_scalers, unsigned int *dev_inc,
     double *dev_pbuf, void *stream);
 
+/* Fused DNA GAMMA traversal (on by default).  The executor above hands
+ * runs of entries to one kernel that keeps each child CLV on chip for its
+ * parent and only writes CLVs to the pool; results are bit-identical to the
+ * per-entry kernels, which remain the path for single-entry launches, for
+ * lists the planner rejects, while profiling is enabled, and when this
+ * switch is off. */
+void examl_hip_use_fused(int on);
+
+/* The fused path's launch planner: plain host code, no GPU call.
+ * Simulates the operand stack of a reference-order entry list (TIP_TIP
+ * pushes, TIP_INNER replaces the top, INNER_INNER pops x2 then x1 and
+ * pushes) with capacity maxDepth (1..16; the executor uses
+ * examl_hip_fused_depth()).  Outputs per entry: launch_of_op (0-based,
+ * non-decreasing), src1/src2 for the x1/x2 operand: -1 = read from the CLV
+ * pool, else the on-chip slot that holds it.  The result of an entry
+ * occupies slot (h % maxDepth), h being the stack height within its launch
+ * after its on-chip operands are popped; a push beyond maxDepth overwrites
+ * the bottom entry.  Tip operands are always -1.  An operand is on chip
+ * only if the same launch produced it and it sits where stack order puts
+ * it; otherwise a new launch starts at that entry.  Launches also end at
+ * examl_hip_fused_max_ops() entries.  Returns the number of launches, or
+ * -1 for a malformed list. */
+int examl_hip_fused_plan(const examl_hip_trav_entry *ops, int numOps,
+                         int maxDepth, int *launch_of_op, int *src1,
+                         int *src2);
+int examl_hip_fused_depth(void);
+int examl_hip_fused_max_ops(void);
+/* most blocks a fused launch uses, and the sites of one tile; blocks
+ * stride over tiles */
+int examl_hip_fused_grid_cap(void);
+int examl_hip_fused_tile_sites(void);
+
 /* replaces the per-partition body of evaluateIterative
  * (examl/evaluateGenericSpecial.c:403): calcDiagptable on the host for the
  * root branch z, upload, then the evaluate kernel including the scaler
