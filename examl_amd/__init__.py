@@ -180,6 +180,10 @@ def _bind(lib):
         [p, i, i, i, i, i, i, p, i, p, p, p, p, p]
     lib.examl_hip_sum_root_multi.argtypes = [p, i, i, i, i, i, p, p]
     lib.examl_hip_core_root_multi.argtypes = [p, p, i, p, p, p, p, p]
+    # on-chip multi-partition traversal: switch, launch counter, tile table
+    lib.examl_hip_multi_use_fused.argtypes = [i]
+    lib.examl_hip_multi_fused_launches.argtypes = [p]
+    lib.examl_hip_multi_tile_table.argtypes = [p, i, i, p, p, i]
     return lib
 
 

@@ -4721,6 +4721,346 @@ __global__ __launch_bounds__(NV_BLOCK) void k_newview_dna_mseg(
   }
 }
 
+/* --- on-chip traversal over all partitions ----------------------------------
+ * The multi-partition form of k_newview_dna_gamma_fused: one launch runs a
+ * whole run of traversal entries per 128-site tile, for every partition, so
+ * a child CLV reaches its parent through registers or the per-thread LDS
+ * stack instead of the pool (every x3 is still stored).  Same program
+ * (FusedProg by value), same operand sources, same thread/unit/tile
+ * geometry as the single-partition kernel.  What differs:
+ *   - a tile table (tilePart/tileSite0, built once per handle by
+ *     examl_hip_multi_tile_table) maps tile -> (partition, first site in
+ *     it); tiles never straddle partitions, so a tile's 4-lane ballot groups
+ *     are whole and a tile has ONE model;
+ *   - per-partition operands come from a descriptor array (MPartDesc);
+ *   - P of (entry e, partition p) is pbuf[((base+e)*numParts+p)*128] and
+ *     its scalerInc inc[(base+e)*numParts+p] (k_make_p_mseg's layout);
+ *   - EV and the thread's tipVector row belong to a partition.  EV is
+ *     double buffered in LDS (sEV[2]); the tipVector row is read straight
+ *     from memory into tv0..tv3.  Both are re-staged, together with op 0's
+ *     P block and ump tables, while the last op of the block's previous
+ *     tile computes;
+ *   - tiles of masked partitions (active[part] == 0) are skipped as if they
+ *     were not in the table: no load, no store, no atomic, no LDS traffic.
+ * Math, summation order, rescale vote and stores restate k_newview_dna_mseg
+ * expression by expression: with the same P block the results are
+ * bit-identical to the level path.
+ *
+ * Barrier rules (as for k_newview_dna_gamma_fused): ONE __syncthreads per
+ * op, reached by every thread of the block on every op of every tile the
+ * block runs.  Which tiles a block runs depends on blockIdx, gridDim, the
+ * tile table and the active flags only, the op loop on prog.count only —
+ * all block-uniform.  Lanes past a partition's last site are predicated
+ * off (`live`) for loads, stores and atomics.  There is no
+ * return/continue/break inside the loops; a block with no tile to run
+ * executes the one prologue barrier and nothing else.  Prefetches for "the
+ * tile after the last one" use the current partition's descriptor and P
+ * block (valid addresses, unused data) with every tip-code lane off.
+ * sEV[x] is rewritten only after a whole tile of the other buffer ran, so
+ * at least one barrier separates its last reader from the write.
+ */
+struct MPartDesc { /* one partition's operands */
+  double *clv;
+  long clvStride;
+  const unsigned char *tips;
+  long tipStride;
+  const int *wgt;
+  const double *EV, *tipVec;
+  long n;
+};
+
+/* Streaming (nontemporal) stores.  A partition with n >= 65536 streams, as
+ * in k_newview_dna_mseg.  A launch whose stores exceed the last-level cache
+ * (FUSED_STREAM_BYTES, the 256 MB Infinity Cache) streams EVERY partition
+ * (streamAll): nothing this launch reads comes from what it wrote, and its
+ * output cannot stay cache-resident for later calls anyway.  Smaller
+ * launches (partial traversals in a search) keep plain stores for narrow
+ * partitions, whose CLVs evaluate_root_multi / sum_root_multi then read
+ * from cache.  A/B log: DESIGN.md §7d.  NT = some tile of this launch may
+ * stream. */
+#define FUSED_STREAM_BYTES (256L << 20)
+
+template <bool NT>
+__global__ __launch_bounds__(NV_BLOCK) void k_newview_dna_mseg_fused(
+    const FusedProg prog, const MPartDesc *__restrict__ parts, int numParts,
+    const int *__restrict__ tilePart, const long *__restrict__ tileSite0,
+    int numTiles, const double *__restrict__ pbuf,
+    unsigned int *__restrict__ inc, const double *__restrict__ active,
+    int streamAll) {
+  __shared__ double sEV[2][16];
+  __shared__ double sP[2][128], sU1[2][256], sU2[2][256];
+  __shared__ v2d sStk[FUSED_D][FUSED_U][2][NV_BLOCK];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int cat = tid & 3;
+  const int count = prog.count;
+  /* ump-table coordinates of this thread (k_newview_dna_mseg's) */
+  const int ucode = tid >> 4, ucat = (tid >> 2) & 3, urow = tid & 3;
+  const int uoff = ucat * 16 + urow * 4;
+
+  /* this block's first unmasked tile */
+  long t = blockIdx.x;
+  while (t < numTiles && active[tilePart[t]] == 0.0) t += gridDim.x;
+  const bool any = t < numTiles;
+  int part = any ? tilePart[t] : 0;
+  long s0 = any ? tileSite0[t] : 0;
+  MPartDesc d = parts[part];
+
+  /* stage op 0 of that tile into buffer 0.  A block whose tiles are all
+   * masked stages nothing: partition 0, whose descriptor it holds, may be
+   * an empty one whose buffers were never allocated. */
+  double tv0 = 0, tv1 = 0, tv2 = 0, tv3 = 0;
+  int c1[FUSED_U], c2[FUSED_U];
+#pragma unroll
+  for (int u = 0; u < FUSED_U; u++) c1[u] = c2[u] = 0;
+  if (any) {
+    tv0 = d.tipVec[ucode * 4 + 0];
+    tv1 = d.tipVec[ucode * 4 + 1];
+    tv2 = d.tipVec[ucode * 4 + 2];
+    tv3 = d.tipVec[ucode * 4 + 3];
+    if (tid < 16) sEV[0][tid] = d.EV[tid];
+    const double *P = pbuf + ((long)prog.base * numParts + part) * 128;
+    const int tc0 = (int)(prog.ctl[0] & 3u);
+    if (tid < 128) sP[0][tid] = P[tid];
+    if (tc0 != EXAML_INNER_INNER) {
+      const double *pl = &P[uoff];
+      sU1[0][tid] = (pl[0] * tv0 + pl[1] * tv1) + (pl[2] * tv2 + pl[3] * tv3);
+      if (tc0 == EXAML_TIP_TIP) {
+        const double *pr = &P[64 + uoff];
+        sU2[0][tid] =
+            (pr[0] * tv0 + pr[1] * tv1) + (pr[2] * tv2 + pr[3] * tv3);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < FUSED_U; u++) {
+      const long site0 = s0 + ((u * NV_BLOCK + tid) >> 2);
+      const bool live0 = site0 < d.n;
+      if (tc0 != EXAML_INNER_INNER && live0)
+        c1[u] = d.tips[(long)prog.x1[0] * d.tipStride + site0];
+      if (tc0 == EXAML_TIP_TIP && live0)
+        c2[u] = d.tips[(long)prog.x2[0] * d.tipStride + site0];
+    }
+  }
+  __syncthreads();
+
+  int buf = 0, evb = 0;
+  double r[FUSED_U][4]; /* previous op's quartets (REG) */
+#pragma unroll
+  for (int u = 0; u < FUSED_U; u++) r[u][0] = r[u][1] = r[u][2] = r[u][3] = 0;
+
+  while (t < numTiles) {
+    const bool nt = NT && (streamAll || d.n >= 65536);
+    for (int e = 0; e < count; e++) {
+      const unsigned int ctl = prog.ctl[e];
+      const int tc = (int)(ctl & 3u);
+
+      /* ---- what comes next: op e+1 of this tile, or op 0 of the block's
+       * next unmasked tile, possibly in another partition ---- */
+      const bool last = e + 1 == count;
+      const int en = last ? 0 : e + 1;
+      long tn = t;
+      if (last)
+        do
+          tn += gridDim.x;
+        while (tn < numTiles && active[tilePart[tn]] == 0.0);
+      const bool more = tn < numTiles;
+      const int partn = (last && more) ? tilePart[tn] : part;
+      const long s0n = (last && more) ? tileSite0[tn] : s0;
+      const bool swap = partn != part;
+      /* the next tile's tip rows (the rest of its descriptor is fetched
+       * when the block gets there: fewer live SGPRs) */
+      const unsigned char *tipsn = d.tips;
+      long tipStriden = d.tipStride, nn = d.n;
+      if (swap) {
+        tipsn = parts[partn].tips;
+        tipStriden = parts[partn].tipStride;
+        nn = parts[partn].n;
+      }
+
+      /* ---- prefetch the next op's staging inputs and tip codes ---- */
+      const int tcn = (int)(prog.ctl[en] & 3u);
+      const double *Pn =
+          pbuf + ((long)(prog.base + en) * numParts + partn) * 128;
+      double pn = 0, pl0 = 0, pl1 = 0, pl2 = 0, pl3 = 0, pr0 = 0, pr1 = 0,
+             pr2 = 0, pr3 = 0;
+      double tvn0 = tv0, tvn1 = tv1, tvn2 = tv2, tvn3 = tv3, evn = 0;
+      int c1n[FUSED_U], c2n[FUSED_U];
+      if (swap) {
+        const double *tvp = parts[partn].tipVec + ucode * 4;
+        tvn0 = tvp[0];
+        tvn1 = tvp[1];
+        tvn2 = tvp[2];
+        tvn3 = tvp[3];
+        if (tid < 16) evn = parts[partn].EV[tid];
+      }
+      if (tid < 128) pn = Pn[tid];
+      if (tcn != EXAML_INNER_INNER) {
+        pl0 = Pn[uoff + 0];
+        pl1 = Pn[uoff + 1];
+        pl2 = Pn[uoff + 2];
+        pl3 = Pn[uoff + 3];
+        if (tcn == EXAML_TIP_TIP) {
+          pr0 = Pn[64 + uoff + 0];
+          pr1 = Pn[64 + uoff + 1];
+          pr2 = Pn[64 + uoff + 2];
+          pr3 = Pn[64 + uoff + 3];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < FUSED_U; u++) {
+        const long siten = s0n + ((u * NV_BLOCK + tid) >> 2);
+        const bool liven = more && siten < nn;
+        c1n[u] = c2n[u] = 0;
+        if (tcn != EXAML_INNER_INNER && liven)
+          c1n[u] = tipsn[(long)prog.x1[en] * tipStriden + siten];
+        if (tcn == EXAML_TIP_TIP && liven)
+          c2n[u] = tipsn[(long)prog.x2[en] * tipStriden + siten];
+      }
+
+      /* ---- op e on this tile ---- */
+      const double *sL = sP[buf], *sR = sP[buf] + 64;
+      const double *ev = sEV[evb];
+#pragma unroll
+      for (int u = 0; u < FUSED_U; u++) {
+        /* unit index within the partition; s0 is a multiple of the tile */
+        const long idx = s0 * 4 + u * NV_BLOCK + tid;
+        const long site = idx >> 2;
+        const bool live = site < d.n;
+        double u1[4], u2[4];
+        if (tc == EXAML_TIP_TIP) {
+#pragma unroll
+          for (int l = 0; l < 4; l++) {
+            u1[l] = sU1[buf][c1[u] * 16 + cat * 4 + l];
+            u2[l] = sU2[buf][c2[u] * 16 + cat * 4 + l];
+          }
+        } else {
+          /* x2 is an inner operand in both remaining cases */
+          double xr0, xr1, xr2, xr3;
+          const unsigned int k2 = (ctl >> 4) & 3u;
+          if (k2 == FSRC_REG) {
+            xr0 = r[u][0]; xr1 = r[u][1]; xr2 = r[u][2]; xr3 = r[u][3];
+          } else if (k2 == FSRC_LDS) {
+            const int sl = (int)((ctl >> 10) & 15u);
+            const v2d lo = sStk[sl][u][0][tid], hi = sStk[sl][u][1][tid];
+            xr0 = lo.x; xr1 = lo.y; xr2 = hi.x; xr3 = hi.y;
+          } else {
+            double4 v = make_double4(0, 0, 0, 0);
+            if (live)
+              v = *reinterpret_cast<const double4 *>(
+                  &d.clv[(long)prog.x2[e] * d.clvStride + idx * 4]);
+            xr0 = v.x; xr1 = v.y; xr2 = v.z; xr3 = v.w;
+          }
+          if (tc == EXAML_INNER_INNER) {
+            double xl0, xl1, xl2, xl3;
+            const unsigned int k1 = (ctl >> 2) & 3u;
+            if (k1 == FSRC_REG) {
+              xl0 = r[u][0]; xl1 = r[u][1]; xl2 = r[u][2]; xl3 = r[u][3];
+            } else if (k1 == FSRC_LDS) {
+              const int sl = (int)((ctl >> 6) & 15u);
+              const v2d lo = sStk[sl][u][0][tid], hi = sStk[sl][u][1][tid];
+              xl0 = lo.x; xl1 = lo.y; xl2 = hi.x; xl3 = hi.y;
+            } else {
+              double4 v = make_double4(0, 0, 0, 0);
+              if (live)
+                v = *reinterpret_cast<const double4 *>(
+                    &d.clv[(long)prog.x1[e] * d.clvStride + idx * 4]);
+              xl0 = v.x; xl1 = v.y; xl2 = v.z; xl3 = v.w;
+            }
+#pragma unroll
+            for (int l = 0; l < 4; l++) {
+              const double *pl = &sL[cat * 16 + l * 4];
+              const double *pr = &sR[cat * 16 + l * 4];
+              u1[l] =
+                  (xl0 * pl[0] + xl1 * pl[1]) + (xl2 * pl[2] + xl3 * pl[3]);
+              u2[l] =
+                  (xr0 * pr[0] + xr1 * pr[1]) + (xr2 * pr[2] + xr3 * pr[3]);
+            }
+          } else {
+#pragma unroll
+            for (int l = 0; l < 4; l++) {
+              const double *pr = &sR[cat * 16 + l * 4];
+              u1[l] = sU1[buf][c1[u] * 16 + cat * 4 + l];
+              u2[l] =
+                  (xr0 * pr[0] + xr1 * pr[1]) + (xr2 * pr[2] + xr3 * pr[3]);
+            }
+          }
+        }
+
+        double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+#pragma unroll
+        for (int l = 0; l < 4; l++) {
+          const double tt = u1[l] * u2[l];
+          a0 += tt * ev[l * 4 + 0];
+          a1 += tt * ev[l * 4 + 1];
+          a2 += tt * ev[l * 4 + 2];
+          a3 += tt * ev[l * 4 + 3];
+        }
+
+        if (tc != EXAML_TIP_TIP) {
+          /* site-wide rescale vote over the site's 4 lanes; lanes past the
+           * partition's end vote "not small" and come in whole groups */
+          const bool small = live & (fabs(a0) < MINLIKELIHOOD) &
+                             (fabs(a1) < MINLIKELIHOOD) &
+                             (fabs(a2) < MINLIKELIHOOD) &
+                             (fabs(a3) < MINLIKELIHOOD);
+          const unsigned long long m = __ballot(small);
+          if (((m >> (lane & ~3)) & 0xFULL) == 0xFULL) {
+            a0 *= TWOTOTHE256;
+            a1 *= TWOTOTHE256;
+            a2 *= TWOTOTHE256;
+            a3 *= TWOTOTHE256;
+            if ((lane & 3) == 0)
+              atomicAdd(inc + (size_t)(prog.base + e) * numParts + part,
+                        (unsigned int)d.wgt[site]);
+          }
+        }
+
+        if (live) {
+          double *x3 = &d.clv[(long)prog.x3[e] * d.clvStride + idx * 4];
+          if (nt)
+            __builtin_nontemporal_store((v4d){a0, a1, a2, a3},
+                                        reinterpret_cast<v4d *>(x3));
+          else
+            *reinterpret_cast<double4 *>(x3) = make_double4(a0, a1, a2, a3);
+        }
+        if (ctl & (1u << 14)) {
+          const int sl = (int)((ctl >> 16) & 15u);
+          sStk[sl][u][0][tid] = (v2d){a0, a1};
+          sStk[sl][u][1][tid] = (v2d){a2, a3};
+        }
+        r[u][0] = a0; r[u][1] = a1; r[u][2] = a2; r[u][3] = a3;
+      }
+
+      /* ---- write the next op's staging into the other buffers (last read
+       * before the previous barrier; the other EV buffer a whole tile
+       * ago) ---- */
+      const int nb = buf ^ 1;
+      if (tid < 128) sP[nb][tid] = pn;
+      if (tcn != EXAML_INNER_INNER) {
+        sU1[nb][tid] = (pl0 * tvn0 + pl1 * tvn1) + (pl2 * tvn2 + pl3 * tvn3);
+        if (tcn == EXAML_TIP_TIP)
+          sU2[nb][tid] =
+              (pr0 * tvn0 + pr1 * tvn1) + (pr2 * tvn2 + pr3 * tvn3);
+      }
+      if (swap && tid < 16) sEV[evb ^ 1][tid] = evn;
+#pragma unroll
+      for (int u = 0; u < FUSED_U; u++) {
+        c1[u] = c1n[u];
+        c2[u] = c2n[u];
+      }
+      __syncthreads();
+      buf = nb;
+      if (swap) evb ^= 1;
+      tv0 = tvn0; tv1 = tvn1; tv2 = tvn2; tv3 = tvn3;
+      if (swap) d = parts[partn];
+      part = partn;
+      s0 = s0n;
+      t = tn;
+    }
+  }
+}
+
 /* fused evaluate, DNA — math identical to k_evaluate_dna_gamma */
 template <bool TIP>
 __global__ __launch_bounds__(NV_BLOCK) void k_evaluate_dna_mseg(
@@ -4983,8 +5323,21 @@ struct examl_hip_multi {
   unsigned int **d_gsArr;
   char *d_callbuf; /* per-call [ESeg|SSeg|CSeg | diag | dtab | active] */
   long callbuf_bytes;
+  /* on-chip traversal (k_newview_dna_mseg_fused), DNA handles only */
+  MPartDesc *d_parts;
+  int *d_tilePart;
+  long *d_tileSite0;
+  int numTiles;
+  bool anyWide;       /* some partition streams its stores */
+  long totalSites;    /* sum of the widths */
+  int lastFused;      /* fused launches of the last traversal call */
   struct Grp {
     int tc, segOff, blkOff, grid;
+  };
+  struct FStep { /* one planner launch: len >= 2 -> progs[idx] through the
+                  * fused kernel, len == 1 -> singles[idx] through
+                  * k_newview_dna_mseg */
+    int len, idx;
   };
   struct Shape {
     unsigned long long key;
@@ -4994,9 +5347,52 @@ struct examl_hip_multi {
     std::vector<int> opLevel; /* per original op, for the finalize */
     int numLevels;
     int numOps;
+    bool fusedOk; /* the planner accepted the list and some launch of its
+                   * plan holds >= 2 entries */
+    std::vector<FStep> fsteps;
+    std::vector<FusedProg> progs;
+    std::vector<Grp> singles;
   };
   std::vector<Shape> shapes;
 };
+
+/* Tile table of the on-chip multi-partition traversal: partition p of width
+ * w owns ceil(w / tileSites) consecutive tiles, in partition order; a
+ * width-0 partition owns none.  Plain host code, no GPU call. */
+static long multi_tile_count(const long *widths, int numParts,
+                             int tileSites) {
+  if (numParts < 0 || tileSites <= 0) return -1;
+  long total = 0;
+  for (int p = 0; p < numParts; p++) {
+    if (widths[p] < 0) return -1;
+    total += (widths[p] + tileSites - 1) / tileSites;
+    if (total > 0x7fffffffL) return -1;
+  }
+  return total;
+}
+
+extern "C" int examl_hip_multi_tile_table(const long *widths, int numParts,
+                                          int tileSites, int *part_of_tile,
+                                          long *site0_of_tile, int cap) {
+  const long total = multi_tile_count(widths, numParts, tileSites);
+  if (total < 0 || cap < 0 || total > cap) return -1;
+  int t = 0;
+  for (int p = 0; p < numParts; p++)
+    for (long s = 0; s < widths[p]; s += tileSites) {
+      part_of_tile[t] = p;
+      site0_of_tile[t] = s;
+      t++;
+    }
+  return t;
+}
+
+static bool g_multi_fused = true;
+
+extern "C" void examl_hip_multi_use_fused(int on) { g_multi_fused = on != 0; }
+
+extern "C" int examl_hip_multi_fused_launches(void *vh) {
+  return vh ? ((examl_hip_multi *)vh)->lastFused : 0;
+}
 
 static int msz_of(int states) { return states + states * states + 4; }
 
@@ -5098,6 +5494,44 @@ extern "C" int examl_hip_multi_create(
                      (long)numParts * 16 * states * sizeof(double) +
                      (long)numParts * sizeof(double);
   MCHK(hipMalloc(&h->d_callbuf, (size_t)h->callbuf_bytes));
+  /* tile table and partition descriptors of the on-chip traversal: they
+   * depend on the widths and buffers only, so they are built once */
+  if (states == 4) {
+    for (int p = 0; p < numParts; p++) {
+      if (widths[p] >= 65536) h->anyWide = true;
+      h->totalSites += widths[p];
+    }
+    /* a handle too wide for the table (or with no site) keeps the level
+     * path: numTiles stays 0 */
+    const long tiles = multi_tile_count(widths, numParts, FUSED_SITES);
+    if (tiles > 0) {
+      std::vector<int> tpart((size_t)tiles);
+      std::vector<long> tsite((size_t)tiles);
+      h->numTiles = examl_hip_multi_tile_table(
+          widths, numParts, FUSED_SITES, tpart.data(), tsite.data(),
+          (int)tiles);
+      if (h->numTiles != (int)tiles) {
+        delete h;
+        snprintf(g_err, sizeof(g_err), "multi_create: tile table");
+        return -1;
+      }
+      std::vector<MPartDesc> desc((size_t)numParts);
+      for (int p = 0; p < numParts; p++)
+        desc[(size_t)p] = {h->clv[p],  h->clvStride[p], h->tips[p],
+                           h->tipStride[p], h->wgt[p],  h->EV[p],
+                           h->tipVec[p],    h->widths[p]};
+      MCHK(hipMalloc(&h->d_tilePart, (size_t)tiles * sizeof(int)));
+      MCHK(hipMalloc(&h->d_tileSite0, (size_t)tiles * sizeof(long)));
+      MCHK(hipMalloc(&h->d_parts, (size_t)numParts * sizeof(MPartDesc)));
+      MCHK(hipMemcpy(h->d_tilePart, tpart.data(),
+                     (size_t)tiles * sizeof(int), hipMemcpyHostToDevice));
+      MCHK(hipMemcpy(h->d_tileSite0, tsite.data(),
+                     (size_t)tiles * sizeof(long), hipMemcpyHostToDevice));
+      MCHK(hipMemcpy(h->d_parts, desc.data(),
+                     (size_t)numParts * sizeof(MPartDesc),
+                     hipMemcpyHostToDevice));
+    }
+  }
 #undef MCHK
   *out = h;
   return 0;
@@ -5115,6 +5549,9 @@ extern "C" void examl_hip_multi_destroy(void *vh) {
   hipFree(h->d_blk2part);
   hipFree(h->d_gsArr);
   hipFree(h->d_callbuf);
+  hipFree(h->d_parts);
+  hipFree(h->d_tilePart);
+  hipFree(h->d_tileSite0);
   for (auto &sh : h->shapes) {
     hipFree(sh.d_segs);
     hipFree(sh.d_blk2seg);
@@ -5142,6 +5579,15 @@ static unsigned long long multi_key(examl_hip_multi *h,
         (unsigned long long)(unsigned)ops[e].x3Slot);
   }
   return x;
+}
+
+/* A shape is looked up by multi_key alone; its cached hipGraph also depends
+ * on which executor the call takes, so that toggling a switch on a live
+ * handle cannot replay the other path's graph. */
+static unsigned long long multi_graph_key(unsigned long long shapeKey,
+                                          bool fused) {
+  return fused ? (shapeKey ^ 0x6f6e63686970ULL) * 0x9e3779b97f4a7c15ULL
+               : shapeKey;
 }
 
 /* build (or fetch) the level/tipCase-grouped segment tables for one
@@ -5191,6 +5637,40 @@ static examl_hip_multi::Shape *multi_shape_get(
    * occupancy and mixes block durations); the templated per-TC groups
    * stay. */
   const int tcGroups = 3;
+  /* the segments of entry e, one per non-empty partition, appended to
+   * group g */
+  auto add_entry_segs = [&](int e, const examl_hip_multi::Grp &g) {
+    const int tc = ops[e].tipCase;
+    for (int p = 0; p < h->numParts; p++) {
+      if (h->widths[p] == 0) continue;
+      MSeg s;
+      memset(&s, 0, sizeof(s));
+      s.x3 = h->clv[p] + (long)ops[e].x3Slot * h->clvStride[p];
+      if (tc == EXAML_TIP_TIP) {
+        s.t1 = h->tips[p] + (long)ops[e].x1Slot * h->tipStride[p];
+        s.t2 = h->tips[p] + (long)ops[e].x2Slot * h->tipStride[p];
+      } else if (tc == EXAML_TIP_INNER) {
+        s.t1 = h->tips[p] + (long)ops[e].x1Slot * h->tipStride[p];
+        s.x2 = h->clv[p] + (long)ops[e].x2Slot * h->clvStride[p];
+      } else {
+        s.x1 = h->clv[p] + (long)ops[e].x1Slot * h->clvStride[p];
+        s.x2 = h->clv[p] + (long)ops[e].x2Slot * h->clvStride[p];
+      }
+      s.P = h->d_pbuf + (long)(e * h->numParts + p) * PBLK;
+      s.wgt = h->wgt[p];
+      s.inc = h->d_inc + (size_t)e * h->numParts + p;
+      s.EV = h->EV[p];
+      s.tipVec = h->tipVec[p];
+      s.n = h->widths[p];
+      s.part = p;
+      s.pad = tc; /* tipCase for the runtime-TC kernel */
+      s.blkBase = (int)blk2seg.size() - g.blkOff;
+      s.nBlocks = h->partBlocks[p];
+      const int si = (int)segs.size();
+      segs.push_back(s);
+      for (int b = 0; b < s.nBlocks; b++) blk2seg.push_back(si);
+    }
+  };
   for (int lv = 0; lv < numLevels; lv++) {
     for (int tcg = 0; tcg < tcGroups; tcg++) {
       examl_hip_multi::Grp g;
@@ -5201,39 +5681,44 @@ static examl_hip_multi::Shape *multi_shape_get(
         if (level[e] != lv ||
             (tcGroups != 1 && ops[e].tipCase != tcg))
           continue;
-        const int tc = ops[e].tipCase;
-        for (int p = 0; p < h->numParts; p++) {
-          if (h->widths[p] == 0) continue;
-          MSeg s;
-          memset(&s, 0, sizeof(s));
-          s.x3 = h->clv[p] + (long)ops[e].x3Slot * h->clvStride[p];
-          if (tc == EXAML_TIP_TIP) {
-            s.t1 = h->tips[p] + (long)ops[e].x1Slot * h->tipStride[p];
-            s.t2 = h->tips[p] + (long)ops[e].x2Slot * h->tipStride[p];
-          } else if (tc == EXAML_TIP_INNER) {
-            s.t1 = h->tips[p] + (long)ops[e].x1Slot * h->tipStride[p];
-            s.x2 = h->clv[p] + (long)ops[e].x2Slot * h->clvStride[p];
-          } else {
-            s.x1 = h->clv[p] + (long)ops[e].x1Slot * h->clvStride[p];
-            s.x2 = h->clv[p] + (long)ops[e].x2Slot * h->clvStride[p];
-          }
-          s.P = h->d_pbuf + (long)(e * h->numParts + p) * PBLK;
-          s.wgt = h->wgt[p];
-          s.inc = h->d_inc + (size_t)e * h->numParts + p;
-          s.EV = h->EV[p];
-          s.tipVec = h->tipVec[p];
-          s.n = h->widths[p];
-          s.part = p;
-          s.pad = tc; /* tipCase for the runtime-TC kernel */
-          s.blkBase = (int)blk2seg.size() - g.blkOff;
-          s.nBlocks = h->partBlocks[p];
-          const int si = (int)segs.size();
-          segs.push_back(s);
-          for (int b = 0; b < s.nBlocks; b++) blk2seg.push_back(si);
-        }
+        add_entry_segs(e, g);
       }
       g.grid = (int)blk2seg.size() - g.blkOff;
       if (g.grid > 0) sh.groups.push_back(g);
+    }
+  }
+  /* on-chip traversal (DNA): the planner's launches in entry order.  A
+   * launch of >= 2 entries is one FusedProg; a launch of one entry gets a
+   * segment group of its own behind the level groups and runs through
+   * k_newview_dna_mseg. */
+  sh.fusedOk = false;
+  if (h->states == 4 && h->numTiles > 0) {
+    std::vector<FusedPlanOp> plan;
+    if (fused_plan(ops, numOps, FUSED_D, FUSED_MAX_OPS, plan) > 0) {
+      for (int e = 0; e < numOps;) {
+        int len = 1;
+        while (e + len < numOps &&
+               plan[(size_t)(e + len)].launch == plan[(size_t)e].launch)
+          len++;
+        if (len >= 2) {
+          sh.fsteps.push_back({len, (int)sh.progs.size()});
+          sh.progs.emplace_back();
+          fused_build_prog(ops, plan, e, len, &sh.progs.back());
+        } else {
+          examl_hip_multi::Grp g;
+          g.tc = ops[e].tipCase;
+          g.segOff = (int)segs.size();
+          g.blkOff = (int)blk2seg.size();
+          add_entry_segs(e, g);
+          g.grid = (int)blk2seg.size() - g.blkOff;
+          sh.fsteps.push_back({1, (int)sh.singles.size()});
+          sh.singles.push_back(g);
+        }
+        e += len;
+      }
+      /* a plan of one-entry launches only has nothing to keep on chip:
+       * it stays on the level path (and its graph) */
+      sh.fusedOk = !sh.progs.empty();
     }
   }
   hipError_t e1 = hipMalloc(&sh.d_segs, segs.size() * sizeof(MSeg));
@@ -5265,6 +5750,7 @@ extern "C" int examl_hip_newview_traversal_multi(
     const double *const *rates, const unsigned char *activeMask,
     const double *qzOv, const double *rzOv, void *stream) {
   examl_hip_multi *h = (examl_hip_multi *)vh;
+  h->lastFused = 0;
   if (numOps <= 0) return 0;
   if (numOps > h->maxOps) {
     snprintf(g_err, sizeof(g_err), "multi traversal: numOps %d > maxOps %d",
@@ -5275,10 +5761,18 @@ extern "C" int examl_hip_newview_traversal_multi(
   (void)hipGetLastError();
   const int S = h->states, NP = h->numParts, MSZ = msz_of(S);
 
-  const unsigned long long key = multi_key(h, ops, numOps, stream);
+  const unsigned long long skey = multi_key(h, ops, numOps, stream);
   int src = 0;
-  examl_hip_multi::Shape *shape = multi_shape_get(h, ops, numOps, key, &src);
+  examl_hip_multi::Shape *shape =
+      multi_shape_get(h, ops, numOps, skey, &src);
   if (!shape) return src;
+  /* DNA: the planner's launches run on chip (k_newview_dna_mseg_fused);
+   * protein handles, rejected lists, the HIP-event profiling mode and
+   * either switch off keep the level path */
+  const bool fused = S == 4 && g_multi_fused && g_use_fused && !g_prof_on &&
+                     shape->fusedOk;
+  const unsigned long long key = multi_graph_key(skey, fused);
+  h->lastFused = fused ? (int)shape->progs.size() : 0;
 
   /* pinned stage: log-z pairs, per-partition model vectors, active flags */
   HostPSlot *slot = hostP_get(h->d_stage, h->stage_doubles);
@@ -5344,6 +5838,44 @@ extern "C" int examl_hip_newview_traversal_multi(
     err = hipGetLastError();
     if (err != hipSuccess) { rc = set_err(err, "make_p launch"); break; }
 
+#define NV_MSEG(K) \
+  hipLaunchKernelGGL((K), dim3(g.grid), dim3(NV_BLOCK), 0, s, dsegs, db2s, \
+                     d_active)
+    if (fused) {
+      /* stream order carries the dependencies between launches */
+      const int fgrid =
+          h->numTiles < FUSED_GRID_CAP ? h->numTiles : FUSED_GRID_CAP;
+      for (auto &st : shape->fsteps) {
+        if (st.len >= 2) {
+          const FusedProg &pg = shape->progs[(size_t)st.idx];
+          /* bytes this launch stores: len CLVs of 16 doubles per site */
+          const int streamAll =
+              (long)st.len * h->totalSites * 128 > FUSED_STREAM_BYTES;
+          if (streamAll || h->anyWide)
+            hipLaunchKernelGGL((k_newview_dna_mseg_fused<true>), dim3(fgrid),
+                               dim3(NV_BLOCK), 0, s, pg, h->d_parts, NP,
+                               h->d_tilePart, h->d_tileSite0, h->numTiles,
+                               h->d_pbuf, h->d_inc, d_active, streamAll);
+          else
+            hipLaunchKernelGGL((k_newview_dna_mseg_fused<false>),
+                               dim3(fgrid), dim3(NV_BLOCK), 0, s, pg,
+                               h->d_parts, NP, h->d_tilePart, h->d_tileSite0,
+                               h->numTiles, h->d_pbuf, h->d_inc, d_active, 0);
+        } else {
+          const examl_hip_multi::Grp &g = shape->singles[(size_t)st.idx];
+          const MSeg *dsegs = shape->d_segs;
+          const int *db2s = shape->d_blk2seg + g.blkOff;
+          switch (g.tc) {
+          case EXAML_TIP_TIP: NV_MSEG(k_newview_dna_mseg<EXAML_TIP_TIP>); break;
+          case EXAML_TIP_INNER:
+            NV_MSEG(k_newview_dna_mseg<EXAML_TIP_INNER>); break;
+          default: NV_MSEG(k_newview_dna_mseg<EXAML_INNER_INNER>);
+          }
+        }
+        err = hipGetLastError();
+        if (err != hipSuccess) { rc = set_err(err, "fused mseg launch"); break; }
+      }
+    } else /* the level path: one launch per (level, tipCase) */
     for (auto &g : shape->groups) {
       hipEvent_t ev_a = nullptr, ev_b = nullptr;
       if (g_prof_on) {
@@ -5352,9 +5884,6 @@ extern "C" int examl_hip_newview_traversal_multi(
       }
       const MSeg *dsegs = shape->d_segs;
       const int *db2s = shape->d_blk2seg + g.blkOff;
-#define NV_MSEG(K) \
-  hipLaunchKernelGGL((K), dim3(g.grid), dim3(NV_BLOCK), 0, s, dsegs, db2s, \
-                     d_active)
       if (S == 4) {
         switch (g.tc) {
         case EXAML_TIP_TIP: NV_MSEG(k_newview_dna_mseg<EXAML_TIP_TIP>); break;

@@ -842,6 +842,11 @@ class MultiEngine:
             _np_vp(rz_a) if rz_a is not None else None,
             self._stream()), "newview_traversal_multi")
 
+    def fused_launches(self):
+        """On-chip kernel launches of the last newview_traversal call (0
+        when it took the level path)."""
+        return lib().examl_hip_multi_fused_launches(self.h)
+
     def evaluate_root(self, tree, p, q, z, active=None, all_reduce=False):
         """z: scalar (joint) or per-partition sequence (-M).  Returns the
         per-partition lnL device vector (sum for the total)."""

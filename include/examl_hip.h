@@ -631,6 +631,32 @@ int examl_hip_core_root_multi(
     const double *const *gammaRates, const unsigned char *activeMask,
     double *dev_out2 /* 2*numParts, caller zeroes */, void *stream);
 
+/* On-chip multi-partition DNA GAMMA traversal.  When this switch and
+ * examl_hip_use_fused are both on, examl_hip_newview_traversal_multi on a
+ * DNA handle walks the launches of the fused planner instead of the
+ * (level x tipCase) groups: a launch of two or more entries is ONE kernel
+ * over the tiles of all partitions that keeps each child CLV on chip for
+ * its parent, a launch of one entry runs the level kernel over that entry.
+ * The P blocks, the scaler increments and the finalize are the level
+ * path's, and CLVs, scalers and lnL are bit-identical to it.  The level
+ * path remains for protein handles, for lists the planner rejects or cuts
+ * into one-entry launches only, while profiling is enabled, and when
+ * either switch is off; toggling a switch on
+ * a live handle never replays the other path's cached graph. */
+void examl_hip_multi_use_fused(int on);
+/* number of on-chip kernel launches the last
+ * examl_hip_newview_traversal_multi call on h issued or replayed from its
+ * graph; 0 when it took the level path */
+int examl_hip_multi_fused_launches(void *h);
+/* The tile table of that kernel: plain host code, no GPU call.  Tiles never
+ * straddle partitions: partition p of width w owns ceil(w / tileSites)
+ * consecutive tiles (none for w == 0), in partition order.  Writes the
+ * partition and the first site within it of every tile and returns the
+ * tile count, or -1 if it exceeds cap (or an argument is malformed). */
+int examl_hip_multi_tile_table(const long *widths, int numParts,
+                               int tileSites, int *part_of_tile,
+                               long *site0_of_tile, int cap);
+
 #ifdef __cplusplus
 }
 #endif
