@@ -91,6 +91,27 @@ def _bind(lib):
         [i, i, i, i, i, p, p, l, p, l, p, l, p]
     lib.examl_hip_core_root_prot_gamma.argtypes = \
         [l, p, p, p, d, p, p, p, p, p]
+    # binary (two-state) surface (same shapes, states=2)
+    lib.examl_host_init_gtr_bin.argtypes = [p, p, p, p, p, p]
+    lib.examl_host_core_dtables_bin.argtypes = [p, p, d, p]
+    lib.examl_hip_newview_bin_gamma.argtypes = \
+        lib.examl_hip_newview_dna_gamma.argtypes
+    lib.examl_hip_evaluate_bin_gamma.argtypes = \
+        lib.examl_hip_evaluate_dna_gamma.argtypes
+    lib.examl_hip_sum_bin_gamma.argtypes = \
+        lib.examl_hip_sum_dna_gamma.argtypes
+    lib.examl_hip_core_bin_gamma.argtypes = \
+        lib.examl_hip_core_dna_gamma.argtypes
+    lib.examl_hip_newview_traversal_bin_gamma.argtypes = \
+        lib.examl_hip_newview_traversal_dna_gamma.argtypes
+    lib.examl_hip_evaluate_root_bin_gamma.argtypes = \
+        lib.examl_hip_evaluate_root_dna_gamma.argtypes
+    lib.examl_hip_sum_root_bin_gamma.argtypes = \
+        lib.examl_hip_sum_root_dna_gamma.argtypes
+    lib.examl_hip_core_root_bin_gamma.argtypes = \
+        lib.examl_hip_core_root_dna_gamma.argtypes
+    lib.examl_hip_bin_force_nt.argtypes = [i]
+    lib.examl_hip_bin_nt_threshold.argtypes = []
     # LG4 (per-category matrices)
     lib.examl_host_make_gamma_cats_median.argtypes = [d, p, i]
     lib.examl_host_make_p_lg4.argtypes = [d, d, p, p, p, p, p]
@@ -211,7 +232,8 @@ def check(rc, what):
             f"{lib().examl_hip_last_error_string().decode()}")
 
 
-from .model import DnaGtrModel, Lg4Model, ProtGtrModel  # noqa: E402
+from .model import (BinGtrModel, DnaGtrModel, Lg4Model,  # noqa: E402
+                    ProtGtrModel)
 from .tree import PhyloTree             # noqa: E402
 from .spr import SprSearch, SprTree     # noqa: E402
 from .engine import (DnaCatEngine, DnaGammaEngine, Lg4Engine,  # noqa: E402
@@ -220,6 +242,7 @@ from .engine import (DnaCatEngine, DnaGammaEngine, Lg4Engine,  # noqa: E402
 
 __all__ = [
     "lib", "check", "TravEntry", "DnaGtrModel", "ProtGtrModel",
+    "BinGtrModel",
     "Lg4Model", "PhyloTree", "SprSearch", "SprTree",
     "DnaGammaEngine", "DnaCatEngine", "Lg4Engine", "SaveDnaEngine",
     "ProtCatEngine", "MultiDnaEngine", "MultiEngine", "SaveProtEngine",

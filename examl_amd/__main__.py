@@ -9,7 +9,8 @@ reference user can point their invocation here unchanged:
 
 Supported: -s -t -g -p -m -f(e|E|d|o|q) -n -w -a -M -S -D -B -c -e -i
 -r -Y -v -R -I, plus AUTO protein partitions (per-partition model
-selection); the binary checkpoint read/write interchange itself lives
+selection) and BINARY/MORPHOLOGICAL partitions (dense GAMMA; not with
+-m PSR, -S or -R); the binary checkpoint read/write interchange itself lives
 in examl_amd.checkpoint.  This is the PRODUCT path: it requires the
 HIP extension and an AMD GPU and fails loudly without one (no CPU
 fallback).
@@ -107,6 +108,12 @@ def _build_engines(parts, opts, device):
             else:
                 engines.append(ea.DnaGammaEngine(p.tips, p.wgt, model,
                                                  device=device))
+        elif p.states == 2:
+            # BINARY/MORPHOLOGICAL: dense GAMMA only (main() has already
+            # refused PSR, -S and -R for such partitions)
+            model = ea.BinGtrModel(p.frequencies, 1.0, use_median=opts["a"])
+            engines.append(ea.DnaGammaEngine(p.tips, p.wgt, model,
+                                             device=device))
         else:
             if p.protModels == AUTO:
                 # AUTO starts as WAG (models.c:4222); protFreqs==0 ->
@@ -189,6 +196,20 @@ def main(argv=None, device=None):
 
     taxa, parts = read_byte_file(opts["s"])
     log(f"partitions: {len(parts)}, taxa: {len(taxa)}, model {opts['m']}")
+    for i, p in enumerate(parts):
+        if p.states == 2:
+            # the reference's per-partition report (axml.c:1447)
+            log(f"Partition: {i}")
+            log("DataType: BINARY/MORPHOLOGICAL")
+            log("Substitution Matrix: Uncorrected")
+    if any(p.states == 2 for p in parts):
+        # binary partitions run the dense GAMMA kernels only
+        for on, what in ((opts["m"] == "PSR", "-m PSR"), (opts["S"], "-S"),
+                         (bool(opts["R"]), "-R")):
+            if on:
+                info_f.close()
+                sys.exit(f"binary (BINARY/MORPHOLOGICAL) partitions are not "
+                         f"supported with {what}")
 
     if opts["R"]:
         # restart (searchAlgo.c:1726): tree from the checkpoint's node
@@ -321,7 +342,7 @@ def main(argv=None, device=None):
                        convergence_criterion=opts["D"],
                        save_best_trees=opts["B"], log=log)
         sp.constraint = cv
-        if (all(p.states == 4 for p in parts)
+        if (all(p.states in (2, 4) for p in parts)
                 and opts["m"] in ("GAMMA", "PSR")
                 and cv is None):
             # resumable like the reference: one binary checkpoint per

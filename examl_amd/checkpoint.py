@@ -48,7 +48,8 @@ NMLNGTH = 256
 
 # pLengths rows (globalVariables.h): states -> (eign, ev, ei, freq, tipvec,
 # subst)
-_PLEN = {4: (4, 16, 16, 4, 64, 6), 20: (20, 400, 400, 20, 460, 190)}
+_PLEN = {4: (4, 16, 16, 4, 64, 6), 20: (20, 400, 400, 20, 460, 190),
+         2: (2, 4, 4, 2, 8, 1)}
 
 REARR_SETTING = 1  # ckp.state (axml.h:655-659)
 FAST_SPRS = 2
@@ -372,7 +373,7 @@ def write_checkpoint(path, tree, models, mxtips, *, state=MOD_OPT,
         buf += np.ascontiguousarray(patrat, np.float64).tobytes()
 
     for m in models:
-        states = 4 if len(m["substRates"]) == 6 else 20
+        states = {6: 4, 1: 2}.get(len(m["substRates"]), 20)
         buf += struct.pack("<i", m["num_cats"])
         psr = np.zeros(MAX_CATEGORIES)
         psr[:len(m["per_site_rates"])] = m["per_site_rates"]
@@ -396,7 +397,7 @@ def write_checkpoint(path, tree, models, mxtips, *, state=MOD_OPT,
                                                 np.float64).tobytes()
         buf += struct.pack("<d", m["alpha"])
         buf += np.ascontiguousarray(m["gammaRates"], np.float64).tobytes()
-        buf += struct.pack("<ii", m.get("protModels", 0 if states == 4
+        buf += struct.pack("<ii", m.get("protModels", 0 if states in (2, 4)
                                         else m.get("protModels", 0)),
                            m.get("autoProtModels", 2))
 
@@ -511,8 +512,8 @@ def build_model_entry(model, num_cats=1, per_site_rates=(1.0,),
     """Convert one of our model objects into the per-model dict of the
     checkpoint layout."""
     states = model.states
-    if states == 4:
-        subst = model.rates6
+    if states in (2, 4):
+        subst = model.rates6 if states == 4 else model.rates1
         prot = 0
         auto = 2
     else:

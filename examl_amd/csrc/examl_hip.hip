@@ -1633,6 +1633,9 @@ extern "C" int examl_hip_core_dna_gamma(long n, const double *sum,
   return 0;
 }
 
+/* binary (two-state) GTRGAMMA kernels and their L0 launchers */
+#include "examl_bin_gamma.inc"
+
 /* --- kernel-time profiling (HIP events on the launch stream) --------------
  * bench.py's roofline leg: when enabled, every newview launch in the
  * traversal executor is bracketed by hipEvent pairs, accumulated per
@@ -2062,7 +2065,7 @@ static int traversal_impl(const examl_hip_trav_entry *ops, int numOps,
 
     /* 2. one newview kernel per entry, post order on one stream
      * (protein uses two lanes per (site,cat) -> 8 units per site) */
-    const int grid = grid_for(n * (STATES == 4 ? 4 : 8));
+    const int grid = grid_for(n * (STATES == 20 ? 8 : 4));
     const bool nt = (STATES == 4) && (n >= 65536);
     /* DNA: runs of >= 2 ops the planner accepts go through the fused
      * kernel; single-op launches, rejected lists and the HIP-event
@@ -2112,6 +2115,19 @@ static int traversal_impl(const examl_hip_trav_entry *ops, int numOps,
       double *x3 = dev_clv + (long)op->x3Slot * clvStride;
       const double *x1 = nullptr, *x2 = nullptr;
       const unsigned char *t1 = nullptr, *t2 = nullptr;
+      if (STATES == 2) {
+        /* binary: one per-entry kernel, its own grid and streaming rule */
+        if (op->tipCase == EXAML_INNER_INNER)
+          x1 = dev_clv + (long)op->x1Slot * clvStride;
+        else
+          t1 = dev_tips + (long)op->x1Slot * tipStride;
+        if (op->tipCase == EXAML_TIP_TIP)
+          t2 = dev_tips + (long)op->x2Slot * tipStride;
+        else
+          x2 = dev_clv + (long)op->x2Slot * clvStride;
+        rc = launch_newview_bin(op->tipCase, s, x1, x2, x3, P, dev_EV,
+                                dev_tipVec, t1, t2, dev_wgt, n, dev_inc + e);
+      } else
       switch (op->tipCase) {
       case EXAML_TIP_TIP:
         t1 = dev_tips + (long)op->x1Slot * tipStride;
@@ -2343,6 +2359,107 @@ extern "C" int examl_hip_core_root_dna_gamma(long n, const double *dev_sum,
   CHK(hipMemcpyAsync(dev_dtab, host48, sizeof(host48), hipMemcpyHostToDevice,
                      s));
   return examl_hip_core_dna_gamma(n, dev_sum, dev_dtab, dev_wgt,
+                                  dev_partials, dev_out2, stream);
+}
+
+/* --- binary (two-state) L1 executors ---------------------------------------
+ * The BINARY_DATA bodies of newviewIterative / evaluateIterative /
+ * makenewzIterative / execCore, shaped like the DNA executors above.
+ */
+
+extern "C" int examl_hip_newview_traversal_bin_gamma(
+    const examl_hip_trav_entry *ops, int numOps, const double *EIGN,
+    const double *EI, const double *gammaRates, const double *dev_EV,
+    const double *dev_tipVec, double *dev_clv, long clvStride,
+    const unsigned char *dev_tips, long tipStride, const int *dev_wgt, long n,
+    unsigned int *dev_scalers, unsigned int *dev_inc, double *dev_pbuf,
+    void *stream) {
+  if (numOps <= 0 || n <= 0) return 0;
+  (void)hipGetLastError();
+  return traversal_impl<2>(ops, numOps, EIGN, EI, gammaRates, dev_EV,
+                           dev_tipVec, dev_clv, clvStride, dev_tips,
+                           tipStride, dev_wgt, n, dev_scalers, dev_inc,
+                           dev_pbuf, (hipStream_t)stream);
+}
+
+extern "C" int examl_hip_evaluate_root_bin_gamma(
+    int rootTipCase, int pNumber, int qNumber, int x1Slot, int x2Slot,
+    int tipSlot, double z, const double *EIGN, const double *gammaRates,
+    const double *dev_tipVec, double *dev_clv, long clvStride,
+    const unsigned char *dev_tips, long tipStride, const int *dev_wgt, long n,
+    const unsigned int *dev_scalers, double *dev_diag, double *dev_partials,
+    double *dev_lnl, void *stream) {
+  if (n <= 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  (void)hipGetLastError(); /* clear stale per-thread error (e.g. torch probes) */
+  double hostDiag[8];
+  examl_host_calc_diagptable(z, 2, 4, gammaRates, EIGN, hostDiag);
+  CHK(hipMemcpyAsync(dev_diag, hostDiag, sizeof(hostDiag),
+                     hipMemcpyHostToDevice, s));
+  const double log_minlik = log(MINLIKELIHOOD);
+  const unsigned int *gsP = dev_scalers ? dev_scalers + pNumber : nullptr;
+  const unsigned int *gsQ = dev_scalers ? dev_scalers + qNumber : nullptr;
+  const double *x1 = nullptr;
+  const unsigned char *t1 = nullptr;
+  if (rootTipCase == EXAML_TIP_INNER) {
+    t1 = dev_tips + (long)tipSlot * tipStride;
+  } else if (rootTipCase == EXAML_INNER_INNER) {
+    x1 = dev_clv + (long)x1Slot * clvStride;
+  } else {
+    snprintf(g_err, sizeof(g_err), "evaluate_root_bin: bad tipCase %d",
+             rootTipCase);
+    return -1;
+  }
+  const double *x2 = dev_clv + (long)x2Slot * clvStride;
+  return examl_hip_evaluate_bin_gamma(dev_wgt, x1, x2, dev_tipVec, t1, n,
+                                      dev_diag, gsP, gsQ, log_minlik,
+                                      dev_partials, dev_lnl, stream);
+}
+
+extern "C" int examl_hip_sum_root_bin_gamma(
+    int rootTipCase, int x1Slot, int x2Slot, int tipSlot, int tipSlot2,
+    const double *dev_tipVec, double *dev_clv, long clvStride,
+    const unsigned char *dev_tips, long tipStride, double *dev_sum, long n,
+    void *stream) {
+  const double *x1 = nullptr, *x2 = nullptr;
+  const unsigned char *t1 = nullptr, *t2 = nullptr;
+  switch (rootTipCase) {
+  case EXAML_TIP_TIP:
+    t1 = dev_tips + (long)tipSlot * tipStride;
+    t2 = dev_tips + (long)tipSlot2 * tipStride;
+    break;
+  case EXAML_TIP_INNER:
+    t1 = dev_tips + (long)tipSlot * tipStride;
+    x2 = dev_clv + (long)x2Slot * clvStride;
+    break;
+  case EXAML_INNER_INNER:
+    x1 = dev_clv + (long)x1Slot * clvStride;
+    x2 = dev_clv + (long)x2Slot * clvStride;
+    break;
+  default:
+    snprintf(g_err, sizeof(g_err), "sum_root_bin: bad tipCase %d",
+             rootTipCase);
+    return -1;
+  }
+  return examl_hip_sum_bin_gamma(rootTipCase, dev_sum, x1, x2, dev_tipVec, t1,
+                                 t2, n, stream);
+}
+
+extern "C" int examl_hip_core_root_bin_gamma(long n, const double *dev_sum,
+                                             const double *EIGN,
+                                             const double *gammaRates,
+                                             double lz, const int *dev_wgt,
+                                             double *dev_dtab,
+                                             double *dev_partials,
+                                             double *dev_out2, void *stream) {
+  if (n <= 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  (void)hipGetLastError(); /* clear stale per-thread error (e.g. torch probes) */
+  double host24[24];
+  examl_host_core_dtables_bin(EIGN, gammaRates, lz, host24);
+  CHK(hipMemcpyAsync(dev_dtab, host24, sizeof(host24), hipMemcpyHostToDevice,
+                     s));
+  return examl_hip_core_bin_gamma(n, dev_sum, dev_dtab, dev_wgt,
                                   dev_partials, dev_out2, stream);
 }
 

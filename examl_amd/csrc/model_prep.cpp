@@ -394,6 +394,34 @@ extern "C" void examl_host_init_gtr_dna(const double *frequencies,
   init_gtr_generic(4, vv, 16, frequencies, rates6, EIGN, EV, EI, tipVector);
 }
 
+/* BINARY: bitVectorIdentity[0..3], getUndetermined=3 (globalVariables.h:146)
+ * — one exchangeability (rates1), tip codes 1 = "0", 2 = "1", 3 = "?"/"-" */
+extern "C" void examl_host_init_gtr_bin(const double *frequencies,
+                                        const double *rates1, double *EIGN,
+                                        double *EV, double *EI,
+                                        double *tipVector) {
+  unsigned int vv[4];
+  for (int i = 0; i < 4; i++) vv[i] = (unsigned int)i;
+  init_gtr_generic(2, vv, 4, frequencies, rates1, EIGN, EV, EI, tipVector);
+}
+
+/* restates the diagptable0/1/2 setup of coreGTRGAMMA_BINARY,
+ * examl/makenewzGenericSpecial.c:1484-1496 */
+extern "C" void examl_host_core_dtables_bin(const double *EIGN,
+                                            const double *gammaRates,
+                                            double lz, double *out24) {
+  double *d0 = out24, *d1 = out24 + 8, *d2 = out24 + 16;
+  for (int i = 0; i < 4; i++) {
+    const double ki = gammaRates[i], kisqr = ki * ki;
+    d0[i * 2] = 1.0;
+    d1[i * 2] = 0.0;
+    d2[i * 2] = 0.0;
+    d0[i * 2 + 1] = exp(EIGN[1] * ki * lz);
+    d1[i * 2 + 1] = EIGN[1] * ki;
+    d2[i * 2 + 1] = EIGN[1] * EIGN[1] * kisqr;
+  }
+}
+
 /* AA: bitVectorAA[23] (globalVariables.h:95) — 20 single-residue bits plus
  * B = D|N, Z = E|Q, X = all */
 extern "C" void examl_host_init_gtr_aa(const double *frequencies,

@@ -28,16 +28,17 @@ def _np_vp(a):
 
 class DnaGammaEngine:
     """Engine for one GTRGAMMA partition slice; `model.states` selects the
-    DNA (4-state) or protein (20-state) kernel family."""
+    DNA (4-state), protein (20-state) or binary (2-state) kernel family."""
 
     def __init__(self, tips, wgt, model, device="cuda", max_ops=None):
         """tips: uint8 [ntips+1, width] (row 0 unused; ambiguity codes —
-        1..15 DNA / 1..22 AA — the yVector of examl/axml.h:599);
-        wgt: int32 [width]; model: DnaGtrModel or ProtGtrModel."""
+        1..15 DNA / 1..22 AA / 1..3 binary — the yVector of examl/axml.h:599);
+        wgt: int32 [width]; model: DnaGtrModel, ProtGtrModel or
+        BinGtrModel."""
         assert tips.dtype == np.uint8 and tips.ndim == 2
         self.states = model.states
         self.SPAN = 4 * self.states
-        self._sfx = "dna" if self.states == 4 else "prot"
+        self._sfx = {4: "dna", 20: "prot", 2: "bin"}[self.states]
         self.ntips = tips.shape[0] - 1
         self.width = tips.shape[1]
         self.ninner = self.ntips - 2

@@ -64,6 +64,42 @@ class DnaGtrModel:
         return DnaGtrModel([0.25] * 4, [1.0] * 6, alpha)
 
 
+class BinGtrModel:
+    """Two-state (BINARY/MORPHOLOGICAL) GTRGAMMA model block — the
+    BINARY_DATA branch of initReversibleGTR (examl/models.c:3483): one
+    exchangeability fixed at 1.0, tip codes 1 = "0", 2 = "1",
+    3 = undetermined."""
+
+    states = 2
+    n_codes = 4
+
+    def __init__(self, frequencies, alpha, use_median=False):
+        self.frequencies = np.ascontiguousarray(frequencies, dtype=np.float64)
+        self.rates1 = np.array([1.0])
+        self.alpha = float(alpha)
+        self.use_median = use_median
+        assert self.frequencies.shape == (2,)
+        self.EIGN = np.zeros(2)
+        self.EV = np.zeros(4)
+        self.EI = np.zeros(4)
+        self.tipVector = np.zeros(8)
+        self.gammaRates = np.zeros(4)
+        self.reinit()
+        self._gamma_cats()
+
+    _gamma_cats = DnaGtrModel._gamma_cats
+
+    def set_alpha(self, alpha):
+        self.alpha = float(alpha)
+        self._gamma_cats()
+
+    def reinit(self):
+        lib().examl_host_init_gtr_bin(_dp(self.frequencies),
+                                      _dp(self.rates1), _dp(self.EIGN),
+                                      _dp(self.EV), _dp(self.EI),
+                                      _dp(self.tipVector))
+
+
 class ProtGtrModel:
     """20-state (protein) GTRGAMMA model block — the AA_DATA branch of
     initReversibleGTR (examl/models.c:3495) with explicit exchangeability

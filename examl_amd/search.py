@@ -90,6 +90,9 @@ class TreeSearch:
                 and all(type(e).__name__ == "DnaGammaEngine"
                         for e in engines)
                 and len({e.states for e in engines}) == 1
+                # MultiEngine knows 4 and 20 states; binary partitions
+                # always run the per-partition loop
+                and engines[0].states in (4, 20)
                 and getattr(engines[0], "device", None) is not None
                 and engines[0].device.type == "cuda"):
             try:
@@ -932,11 +935,13 @@ class TreeSearch:
                                         RATE_F, model_epsilon)
         # AA GTR rate optimization only applies to protModels==GTR
         # partitions (AAisGTR, optimizeModel.c:1614) — LG et al. are fixed.
+        # binary: numberOfRates = (2*2 - 2)/2 - 1 = 0 (optRates,
+        # optimizeModel.c:1607) — nothing to optimize.
 
     def opt_alphas_generic(self, model_epsilon):
         """optAlphasGeneric (optimizeModel.c:1136): plain-alpha partitions
-        via ALPHA_F, then LG4X partitions via optLG4X (LXRATE_F sweeps +
-        weight optimization)."""
+        (DNA, binary and non-LG4X protein) via ALPHA_F, then LG4X
+        partitions via optLG4X (LXRATE_F sweeps + weight optimization)."""
         groups = [[m] for m in range(self.M)]
         is_lg4x = [getattr(self.engines[m].model, "lg4x", False)
                    for m in range(self.M)]
@@ -979,6 +984,13 @@ class TreeSearch:
         if any(aa_valid):
             for rn in range(20):
                 self._opt_param_generic(groups, aa_valid, rn, -1000000.0,
+                                        200.0, FREQ_F, model_epsilon)
+        # then binary (optimizeModel.c:1568-1594)
+        bin_valid = [self.engines[m].model.states == 2
+                     and self.opt_freq_flags[m] for m in range(self.M)]
+        if any(bin_valid):
+            for rn in range(2):
+                self._opt_param_generic(groups, bin_valid, rn, -1000000.0,
                                         200.0, FREQ_F, model_epsilon)
 
     # -- AUTO protein model selection (optimizeModel.c:2606-2900) ----------

@@ -426,6 +426,118 @@ int examl_hip_core_root_prot_gamma(long n, const double *dev_sum,
                                    void *stream);
 
 
+/* ---------------------------------------------------------------------------
+ * Binary (two-state, BINARY/MORPHOLOGICAL) GTRGAMMA surface — span 8, CLV
+ * x[site*8 + cat*2 + state], tip codes 1..3 (3 = undetermined).  P blocks
+ * are 32 doubles (left 16 | right 16, left[cat*4 + row*2 + col]), diag 8,
+ * dtables 24.  examl_host_make_p and examl_host_calc_diagptable take
+ * states = 2 as they are.  Dense GAMMA, one engine per partition: there is
+ * no CAT/PSR, -S, on-chip fused or multi-partition variant for two states.
+ * ------------------------------------------------------------------------ */
+
+/* replaces initReversibleGTR -> initGeneric for BINARY_DATA
+ * (examl/models.c:3483-3493; bit vector and undetermined code of
+ * examl/globalVariables.h:146): states=2, 4 tip codes, one exchangeability;
+ * emits EIGN[2], EV[4], EI[4], tipVector[8]. */
+void examl_host_init_gtr_bin(const double *frequencies, const double *rates1,
+                             double *EIGN, double *EV, double *EI,
+                             double *tipVector);
+
+/* d0/d1/d2 tables of coreGTRGAMMA_BINARY
+ * (examl/makenewzGenericSpecial.c:1484-1496): out24 = {d0[8], d1[8],
+ * d2[8]}, each [cat*2 + state]. */
+void examl_host_core_dtables_bin(const double *EIGN, const double *gammaRates,
+                                 double lz, double *out24);
+
+/* replaces newviewGTRGAMMA_BINARY (examl/newviewGenericSpecial.c:6034):
+ * x3[cat][j] = sum_l ((x1 . L[cat][l]) * (x2 . R[cat][l])) * EV[2l + j],
+ * with the reference's 2^-256 rescale rule over the 8 span entries of a
+ * site (TIP_INNER / INNER_INNER only) and scaler counts accumulated as the
+ * sum of wgt[site] into *dev_scalerInc (device, caller zeroes).
+ * dev_right must be dev_left + 16 (one 32-double P block). */
+int examl_hip_newview_bin_gamma(int tipCase, const double *dev_x1,
+                                const double *dev_x2, double *dev_x3,
+                                const double *dev_EV,
+                                const double *dev_tipVector,
+                                const unsigned char *dev_tipX1,
+                                const unsigned char *dev_tipX2, long n,
+                                const double *dev_left,
+                                const double *dev_right, const int *dev_wgt,
+                                unsigned int *dev_scalerInc, void *stream);
+
+/* replaces evaluateGTRGAMMA_BINARY (examl/evaluateGenericSpecial.c:1074)
+ * plus the scaler undo at :830; arguments as examl_hip_evaluate_dna_gamma. */
+int examl_hip_evaluate_bin_gamma(const int *dev_wgt, const double *dev_x1,
+                                 const double *dev_x2,
+                                 const double *dev_tipVector,
+                                 const unsigned char *dev_tipX1, long n,
+                                 const double *dev_diag,
+                                 const unsigned int *dev_gsP,
+                                 const unsigned int *dev_gsQ,
+                                 double log_minlik, double *dev_partials,
+                                 double *dev_lnl, void *stream);
+
+/* replaces sumGAMMA_BINARY (examl/makenewzGenericSpecial.c:1543). */
+int examl_hip_sum_bin_gamma(int tipCase, double *dev_sum,
+                            const double *dev_x1, const double *dev_x2,
+                            const double *dev_tipVector,
+                            const unsigned char *dev_tipX1,
+                            const unsigned char *dev_tipX2, long n,
+                            void *stream);
+
+/* replaces coreGTRGAMMA_BINARY (examl/makenewzGenericSpecial.c:1464);
+ * dev_dtables holds the 24 doubles of examl_host_core_dtables_bin. */
+int examl_hip_core_bin_gamma(long n, const double *dev_sum,
+                             const double *dev_dtables, const int *dev_wgt,
+                             double *dev_partials, double *dev_out2,
+                             void *stream);
+
+/* L1 executors: the BINARY_DATA bodies of newviewIterative
+ * (examl/newviewGenericSpecial.c:917), evaluateIterative
+ * (examl/evaluateGenericSpecial.c:403), makenewzIterative's sum precompute
+ * (examl/makenewzGenericSpecial.c:628) and execCore (:849).  Argument lists
+ * are those of the _dna_gamma executors; dev_pbuf >= numOps*32 doubles,
+ * dev_diag_scratch >= 8, dev_dtab_scratch >= 24.  One kernel per entry:
+ * the on-chip fused traversal is DNA only. */
+int examl_hip_newview_traversal_bin_gamma(
+    const examl_hip_trav_entry *ops, int numOps, const double *EIGN,
+    const double *EI, const double *gammaRates, const double *dev_EV,
+    const double *dev_tipVector, double *dev_clv, long clvStrideDoubles,
+    const unsigned char *dev_tips, long tipStrideBytes, const int *dev_wgt,
+    long n, unsigned int *dev_scalers, unsigned int *dev_inc,
+    double *dev_pbuf, void *stream);
+
+int examl_hip_evaluate_root_bin_gamma(
+    int rootTipCase, int pNumber, int qNumber, int x1Slot, int x2Slot,
+    int tipSlot, double z, const double *EIGN, const double *gammaRates,
+    const double *dev_tipVector, double *dev_clv, long clvStrideDoubles,
+    const unsigned char *dev_tips, long tipStrideBytes, const int *dev_wgt,
+    long n, const unsigned int *dev_scalers, double *dev_diag_scratch,
+    double *dev_partials, double *dev_lnl, void *stream);
+
+int examl_hip_sum_root_bin_gamma(int rootTipCase, int x1Slot, int x2Slot,
+                                 int tipSlot, int tipSlot2,
+                                 const double *dev_tipVector, double *dev_clv,
+                                 long clvStrideDoubles,
+                                 const unsigned char *dev_tips,
+                                 long tipStrideBytes, double *dev_sum, long n,
+                                 void *stream);
+
+int examl_hip_core_root_bin_gamma(long n, const double *dev_sum,
+                                  const double *EIGN,
+                                  const double *gammaRates, double lz,
+                                  const int *dev_wgt,
+                                  double *dev_dtab_scratch,
+                                  double *dev_partials, double *dev_out2,
+                                  void *stream);
+
+/* Streaming-store rule of the binary newview kernels, for measurements:
+ * -1 = by size (the default: n >= 131072 sites, 8 MB per CLV), 0 = never,
+ * 1 = always.  Results are bit-identical under every setting. */
+void examl_hip_bin_force_nt(int mode);
+int examl_hip_bin_nt_threshold(void);
+
+
 /* ---- LG4 (LG4M/LG4X): per-gamma-category matrices --------------------- */
 /* Host model math (model_prep.cpp): EIGN4 stride 20 (scaled), EI4 stride
  * 400, tipVector4 stride 460, EV4 stride 400. */

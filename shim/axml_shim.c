@@ -142,6 +142,12 @@ static void init_part(tree *tr, int m)
   int states = pd->states;
   int mxtips = tr->mxtips;
 
+  if (states == 2) {
+    /* BINARY_DATA would otherwise fall into the protein branches below */
+    fprintf(stderr, "examl-HIP shim: binary partitions are not supported by "
+                    "the hybrid binary (use python -m examl_amd)\n");
+    MPI_Abort(MPI_COMM_WORLD, 1);
+  }
   if (states != 4 && states != 20) {
     fprintf(stderr,
             "examl-HIP shim: %d-state partitions are not supported\n",
