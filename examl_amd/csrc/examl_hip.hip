@@ -25,6 +25,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "../../include/examl_hip.h"
 
 /* constants — reference examl/axml.h:110-117 */
@@ -40,6 +42,12 @@ static int set_err(hipError_t e, const char *where) {
   snprintf(g_err, sizeof(g_err), "%s: %s", where, hipGetErrorString(e));
   return (int)e;
 }
+
+#define CHK(call)                                                              \
+  do {                                                                         \
+    hipError_t _e = (call);                                                    \
+    if (_e != hipSuccess) return set_err(_e, #call);                           \
+  } while (0)
 
 extern "C" const char *examl_hip_version(void) { return "examl_amd 0.1 gfx950"; }
 extern "C" const char *examl_hip_last_error_string(void) { return g_err; }
@@ -1505,11 +1513,89 @@ extern "C" void examl_host_core_dtables_dna_cat(const double *EIGN,
  * Launchers
  * ==========================================================================*/
 
-#define CHK(call)                                                              \
-  do {                                                                         \
-    hipError_t _e = (call);                                                    \
-    if (_e != hipSuccess) return set_err(_e, #call);                           \
-  } while (0)
+static bool g_fast_math = false; /* examl_hip_fast_math */
+
+/* Hand a runtime tipCase / flag on as a compile-time constant:
+ * f(std::integral_constant) picks the template instantiation to launch.
+ * with_tip_case returns false, without calling f, for an unknown tipCase. */
+template <class F>
+static bool with_tip_case(int tipCase, F &&f) {
+  switch (tipCase) {
+  case EXAML_TIP_TIP:
+    f(std::integral_constant<int, EXAML_TIP_TIP>{});
+    return true;
+  case EXAML_TIP_INNER:
+    f(std::integral_constant<int, EXAML_TIP_INNER>{});
+    return true;
+  case EXAML_INNER_INNER:
+    f(std::integral_constant<int, EXAML_INNER_INNER>{});
+    return true;
+  }
+  return false;
+}
+
+template <class F>
+static void with_flag(bool on, F &&f) {
+  if (on)
+    f(std::true_type{});
+  else
+    f(std::false_type{});
+}
+
+/* One newview launch of a family, shared by its L0 entry point and its
+ * traversal executor; false = unknown tipCase, nothing launched.  The
+ * caller reads hipGetLastError. */
+static bool launch_newview_dna_gamma(
+    int tipCase, bool nt, hipStream_t s, const double *x1, const double *x2,
+    double *x3, const double *P, const double *EV, const double *tipVec,
+    const unsigned char *t1, const unsigned char *t2, const int *wgt, long n,
+    unsigned int *inc) {
+  const int grid = grid_for(n * 4);
+  return with_tip_case(tipCase, [&](auto tc) {
+    with_flag(nt, [&](auto ntc) {
+      hipLaunchKernelGGL(
+          (k_newview_dna_gamma<decltype(tc)::value, decltype(ntc)::value>),
+          dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, P, EV, tipVec, t1, t2,
+          wgt, n, inc);
+    });
+  });
+}
+
+static bool launch_newview_prot_gamma(
+    int tipCase, bool nt, hipStream_t s, const double *x1, const double *x2,
+    double *x3, const double *P, const double *EV, const double *tipVec,
+    const unsigned char *t1, const unsigned char *t2, const int *wgt, long n,
+    unsigned int *inc) {
+  const int grid = grid_for(n * 8); /* two lanes per (site,cat) */
+  return with_tip_case(tipCase, [&](auto tc) {
+    with_flag(nt, [&](auto ntc) {
+      with_flag(g_fast_math, [&](auto fast) {
+        hipLaunchKernelGGL(
+            (k_newview_prot_gamma<decltype(tc)::value, decltype(ntc)::value,
+                                  decltype(fast)::value>),
+            dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, P, EV, tipVec, t1,
+            t2, wgt, n, inc);
+      });
+    });
+  });
+}
+
+static bool launch_newview_dna_cat(
+    int tipCase, hipStream_t s, const double *EV, const int *cptr,
+    const double *x1, const double *x2, double *x3, const double *tipVec,
+    const unsigned char *t1, const unsigned char *t2, const int *wgt, long n,
+    const double *P, int numCats, unsigned int *inc) {
+  const int grid = grid_for(n);
+  const bool nt = n >= 262144; /* 32 B/site write */
+  return with_tip_case(tipCase, [&](auto tc) {
+    with_flag(nt, [&](auto ntc) {
+      hipLaunchKernelGGL(
+          (k_newview_dna_cat<decltype(tc)::value, decltype(ntc)::value>),
+          dim3(grid), dim3(NV_BLOCK), 0, s, EV, cptr, x1, x2, x3, tipVec, t1,
+          t2, wgt, n, P, numCats, inc);
+    });
+  });
+}
 
 extern "C" int examl_hip_newview_dna_gamma(
     int tipCase, const double *x1, const double *x2, double *x3,
@@ -1518,9 +1604,7 @@ extern "C" int examl_hip_newview_dna_gamma(
     const double *right, const int *wgt, unsigned int *scalerInc,
     void *stream) {
   if (n <= 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
   (void)hipGetLastError(); /* clear stale per-thread error (e.g. torch probes) */
-  const int grid = grid_for(n * 4);
   const bool nt = n >= 65536; /* streaming stores once x3 exceeds L2 */
   /* left/right must be contiguous (P = left | right); the launcher copies
    * are avoided by requiring the caller to pass left==P, right==P+64 when
@@ -1531,26 +1615,9 @@ extern "C" int examl_hip_newview_dna_gamma(
              "newview: right must be left+64 (one 128-double P block)");
     return -1;
   }
-  switch (tipCase) {
-  case EXAML_TIP_TIP:
-    if (nt)
-      hipLaunchKernelGGL((k_newview_dna_gamma<EXAML_TIP_TIP, true>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, left, EV, tipVec, tipX1, tipX2, wgt, n, scalerInc);
-    else
-      hipLaunchKernelGGL((k_newview_dna_gamma<EXAML_TIP_TIP, false>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, left, EV, tipVec, tipX1, tipX2, wgt, n, scalerInc);
-    break;
-  case EXAML_TIP_INNER:
-    if (nt)
-      hipLaunchKernelGGL((k_newview_dna_gamma<EXAML_TIP_INNER, true>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, left, EV, tipVec, tipX1, tipX2, wgt, n, scalerInc);
-    else
-      hipLaunchKernelGGL((k_newview_dna_gamma<EXAML_TIP_INNER, false>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, left, EV, tipVec, tipX1, tipX2, wgt, n, scalerInc);
-    break;
-  case EXAML_INNER_INNER:
-    if (nt)
-      hipLaunchKernelGGL((k_newview_dna_gamma<EXAML_INNER_INNER, true>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, left, EV, tipVec, tipX1, tipX2, wgt, n, scalerInc);
-    else
-      hipLaunchKernelGGL((k_newview_dna_gamma<EXAML_INNER_INNER, false>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, left, EV, tipVec, tipX1, tipX2, wgt, n, scalerInc);
-    break;
-  default:
+  if (!launch_newview_dna_gamma(tipCase, nt, (hipStream_t)stream, x1, x2, x3,
+                                left, EV, tipVec, tipX1, tipX2, wgt, n,
+                                scalerInc)) {
     snprintf(g_err, sizeof(g_err), "newview: bad tipCase %d", tipCase);
     return -1;
   }
@@ -1710,7 +1777,6 @@ struct TravGraph {
 };
 static thread_local std::vector<TravGraph> g_graphs;
 static bool g_use_graphs = true;
-static bool g_fast_math = false;
 static bool g_use_fused = true;
 
 extern "C" void examl_hip_fast_math(int on) { g_fast_math = on != 0; }
@@ -2001,19 +2067,155 @@ static void fused_build_prog(const examl_hip_trav_entry *ops,
   }
 }
 
-/* --- batched traversal (newviewIterative body) --------------------------- */
+/* --- graph shell -----------------------------------------------------------
+ * Runs `body`, which enqueues one traversal on stream `s` and returns 0 or
+ * an error, through the graph cache: a cached `key` is replayed; otherwise
+ * `body` is captured, instantiated, stored and launched.  Without
+ * `want_graph`, or when the capture cannot begin, `body` runs directly.
+ * Whatever `body` reads on the host must be filled before the call: a
+ * replay does not run it, and a failed capture runs it twice. */
+template <class Body>
+static int with_graph(unsigned long long key, bool want_graph, hipStream_t s,
+                      Body &&body) {
+  if (!want_graph) return body();
+  if (hipGraphExec_t cached = trav_graph_find(key)) {
+    CHK(hipGraphLaunch(cached, s));
+    return 0;
+  }
+  const bool capturing =
+      hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess;
+  (void)hipGetLastError();
+  const int rc = body();
+  if (!capturing) return rc;
+  hipGraph_t graph = nullptr;
+  hipError_t err = hipStreamEndCapture(s, &graph);
+  if (rc != 0) {
+    if (graph) (void)hipGraphDestroy(graph);
+    return rc;
+  }
+  hipGraphExec_t exec = nullptr;
+  if (err == hipSuccess) {
+    err = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+  }
+  if (err != hipSuccess) {
+    /* the captured sequence never executed: disable graphs and run it for
+     * real */
+    (void)hipGetLastError();
+    g_use_graphs = false;
+    return body();
+  }
+  trav_graph_store(key, exec);
+  CHK(hipGraphLaunch(exec, s));
+  return 0;
+}
 
-template <int STATES>
-static int traversal_impl(const examl_hip_trav_entry *ops, int numOps,
-                          const double *EIGN, const double *EI,
-                          const double *gammaRates, const double *dev_EV,
-                          const double *dev_tipVec, double *dev_clv,
-                          long clvStride, const unsigned char *dev_tips,
-                          long tipStride, const int *dev_wgt, long n,
-                          unsigned int *dev_scalers, unsigned int *dev_inc,
-                          double *dev_pbuf, hipStream_t s) {
-  constexpr int PBLK = 8 * STATES * STATES; /* left|right, 4 cats */
-  HostPSlot *pslot = hostP_get(dev_pbuf, (size_t)numOps * PBLK);
+/* --- batched traversal (newviewIterative body) -----------------------------
+ * One driver for every single-partition family.  A family is a TravCall
+ * (its buffers and the three numbers that tell families apart) plus two
+ * callables: make_p fills one entry's P block on the host, launch_entry
+ * launches the newview kernel(s).
+ */
+struct TravCall {
+  const char *family; /* prefix of the error strings */
+  int tag;            /* graph-key tag: keeps the families apart */
+  long pblk;          /* doubles per entry in pbuf: left | right */
+  const examl_hip_trav_entry *ops;
+  int numOps;
+  const double *EV, *tipVec;
+  const int *cptr; /* CAT: per-site rate category; else null */
+  double *clv;
+  long clvStride;
+  const unsigned char *tips;
+  long tipStride;
+  const int *wgt;
+  long n;
+  unsigned int *scalers, *inc;
+  double *pbuf;
+  hipStream_t stream;
+};
+
+/* the device operands of one entry */
+struct TravOperands {
+  const double *x1, *x2; /* inner children (else null) */
+  const unsigned char *t1, *t2; /* tip children (else null) */
+  double *x3;
+  const double *P;   /* the entry's block in pbuf */
+  unsigned int *inc; /* the entry's scaler increment */
+};
+
+/* tipCase + child slots -> x1/x2/t1/t2; -1 and "<family>: bad tipCase" for
+ * an unknown tipCase */
+static int trav_operands(int tipCase, int slot1, int slot2, double *clv,
+                         long clvStride, const unsigned char *tips,
+                         long tipStride, const char *family,
+                         TravOperands *o) {
+  *o = TravOperands{};
+  switch (tipCase) {
+  case EXAML_TIP_TIP:
+    o->t1 = tips + (long)slot1 * tipStride;
+    o->t2 = tips + (long)slot2 * tipStride;
+    return 0;
+  case EXAML_TIP_INNER:
+    o->t1 = tips + (long)slot1 * tipStride;
+    o->x2 = clv + (long)slot2 * clvStride;
+    return 0;
+  case EXAML_INNER_INNER:
+    o->x1 = clv + (long)slot1 * clvStride;
+    o->x2 = clv + (long)slot2 * clvStride;
+    return 0;
+  }
+  snprintf(g_err, sizeof(g_err), "%s: bad tipCase %d", family, tipCase);
+  return -1;
+}
+
+static int trav_operands(const examl_hip_trav_entry *op, const TravCall &c,
+                         TravOperands *o) {
+  if (trav_operands(op->tipCase, op->x1Slot, op->x2Slot, c.clv, c.clvStride,
+                    c.tips, c.tipStride, c.family, o) != 0)
+    return -1;
+  o->x3 = c.clv + (long)op->x3Slot * c.clvStride;
+  o->P = c.pbuf + (op - c.ops) * c.pblk;
+  o->inc = c.inc + (op - c.ops);
+  return 0;
+}
+
+/* the root branch of examl_hip_sum_root_*: a tip child comes by tip slot */
+static int sum_root_operands(int rootTipCase, int x1Slot, int x2Slot,
+                             int tipSlot, int tipSlot2, double *clv,
+                             long clvStride, const unsigned char *tips,
+                             long tipStride, const char *family,
+                             TravOperands *o) {
+  return trav_operands(rootTipCase,
+                       rootTipCase == EXAML_INNER_INNER ? x1Slot : tipSlot,
+                       rootTipCase == EXAML_TIP_TIP ? tipSlot2 : x2Slot, clv,
+                       clvStride, tips, tipStride, family, o);
+}
+
+/* make_p callable of the families whose P blocks come from
+ * examl_host_make_p */
+static auto host_make_p(const double *rates, const double *EI,
+                        const double *EIGN, int numCats, int states) {
+  return [=](double qz, double rz, double *left, double *right) {
+    examl_host_make_p(qz, rz, rates, EI, EIGN, numCats, left, right, states);
+  };
+}
+
+static int trav_err(const TravCall &c, hipError_t e, const char *step) {
+  char where[64];
+  snprintf(where, sizeof(where), "%s %s", c.family, step);
+  return set_err(e, where);
+}
+
+/* launch_entry(e, operands) launches entry e and returns how many entries
+ * it consumed (a fused launch takes several), or 0 with g_err set. */
+template <class MakeP, class LaunchEntry>
+static int run_traversal(const TravCall &c, MakeP &&make_p,
+                         LaunchEntry &&launch_entry) {
+  const examl_hip_trav_entry *ops = c.ops;
+  const int numOps = c.numOps;
+  hipStream_t s = c.stream;
+  HostPSlot *pslot = hostP_get(c.pbuf, (size_t)numOps * c.pblk);
   double *hostP = pslot->buf;
 
   /* 1. all P-matrix pairs on the host (newviewGenericSpecial.c:982-1044) */
@@ -2021,8 +2223,7 @@ static int traversal_impl(const examl_hip_trav_entry *ops, int numOps,
     double qz = ops[e].qz, rz = ops[e].rz;
     qz = (qz > ZMIN) ? log(qz) : log(ZMIN);
     rz = (rz > ZMIN) ? log(rz) : log(ZMIN);
-    examl_host_make_p(qz, rz, gammaRates, EI, EIGN, 4, &hostP[e * PBLK],
-                      &hostP[e * PBLK + PBLK / 2], STATES);
+    make_p(qz, rz, &hostP[e * c.pblk], &hostP[e * c.pblk + c.pblk / 2]);
   }
 
   /* graph fast path: identical traversal shape -> replay (P content flows
@@ -2033,182 +2234,50 @@ static int traversal_impl(const examl_hip_trav_entry *ops, int numOps,
   const bool want_graph =
       g_use_graphs && !g_prof_on && s != nullptr && numOps >= 8;
   unsigned long long key = 0;
-  bool capturing = false;
   if (want_graph) {
-    key = trav_key(ops, numOps, n, dev_clv, dev_tips, dev_pbuf, dev_EV,
-                   dev_tipVec, dev_wgt, dev_scalers, dev_inc, (void *)s,
-                   STATES);
-    hipGraphExec_t exec = trav_graph_find(key);
-    if (exec) {
-      CHK(hipGraphLaunch(exec, s));
-      return 0;
-    }
-    capturing =
-        hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) ==
-        hipSuccess;
-    (void)hipGetLastError();
+    key = trav_key(ops, numOps, c.n, c.clv, c.tips, c.pbuf, c.EV, c.tipVec,
+                   c.wgt, c.scalers, c.inc, (void *)s, c.tag);
+    /* a replay binds the category array like any other buffer */
+    if (c.cptr)
+      key = (key ^ (unsigned long long)(uintptr_t)c.cptr) * 1099511628211ULL;
   }
 
-  int rc = 0;
-  do {
-    hipError_t err = hipMemcpyAsync(dev_pbuf, hostP,
-                                    (size_t)numOps * PBLK * sizeof(double),
+  return with_graph(key, want_graph, s, [&]() -> int {
+    hipError_t err = hipMemcpyAsync(c.pbuf, hostP,
+                                    (size_t)numOps * c.pblk * sizeof(double),
                                     hipMemcpyHostToDevice, s);
-    if (err != hipSuccess) { rc = set_err(err, "pbuf upload"); break; }
+    if (err != hipSuccess) return trav_err(c, err, "pbuf upload");
     /* completion marker for the NEXT refill of this slot (captured as a
      * graph node when capturing, so replays re-record it) */
-    hipEventRecord(pslot->ev, s);
+    (void)hipEventRecord(pslot->ev, s);
     pslot->ev_valid = true;
-    err = hipMemsetAsync(dev_inc, 0, (size_t)numOps * sizeof(unsigned int),
-                         s);
-    if (err != hipSuccess) { rc = set_err(err, "inc memset"); break; }
+    err = hipMemsetAsync(c.inc, 0, (size_t)numOps * sizeof(unsigned int), s);
+    if (err != hipSuccess) return trav_err(c, err, "inc memset");
 
-    /* 2. one newview kernel per entry, post order on one stream
-     * (protein uses two lanes per (site,cat) -> 8 units per site) */
-    const int grid = grid_for(n * (STATES == 20 ? 8 : 4));
-    const bool nt = (STATES == 4) && (n >= 65536);
-    /* DNA: runs of >= 2 ops the planner accepts go through the fused
-     * kernel; single-op launches, rejected lists and the HIP-event
-     * profiling mode keep the per-op kernels below */
-    std::vector<FusedPlanOp> plan;
-    std::vector<int> fused_len((size_t)numOps, 0);
-    if (STATES == 4 && g_use_fused && !g_prof_on &&
-        fused_plan(ops, numOps, FUSED_D, FUSED_MAX_OPS, plan) > 0) {
-      for (int e = 0; e < numOps;) {
-        int len = 1;
-        while (e + len < numOps &&
-               plan[(size_t)(e + len)].launch == plan[(size_t)e].launch)
-          len++;
-        fused_len[(size_t)e] = len;
-        e += len;
-      }
-    }
-    for (int e = 0; e < numOps && rc == 0; e++) {
-      const examl_hip_trav_entry *op = &ops[e];
-      if (fused_len[(size_t)e] >= 2) {
-        FusedProg pg;
-        fused_build_prog(ops, plan, e, fused_len[(size_t)e], &pg);
-        const long tiles = (n + FUSED_SITES - 1) / FUSED_SITES;
-        const int fgrid =
-            (int)(tiles < FUSED_GRID_CAP ? tiles : FUSED_GRID_CAP);
-        if (nt)
-          hipLaunchKernelGGL((k_newview_dna_gamma_fused<true>), dim3(fgrid),
-                             dim3(NV_BLOCK), 0, s, pg, dev_clv, clvStride,
-                             dev_tips, tipStride, dev_pbuf, dev_EV,
-                             dev_tipVec, dev_wgt, n, dev_inc);
-        else
-          hipLaunchKernelGGL((k_newview_dna_gamma_fused<false>), dim3(fgrid),
-                             dim3(NV_BLOCK), 0, s, pg, dev_clv, clvStride,
-                             dev_tips, tipStride, dev_pbuf, dev_EV,
-                             dev_tipVec, dev_wgt, n, dev_inc);
-        err = hipGetLastError();
-        if (err != hipSuccess) { rc = set_err(err, "fused newview launch"); break; }
-        e += fused_len[(size_t)e] - 1;
-        continue;
-      }
+    /* 2. newview kernels in post order on one stream, each launch bracketed
+     * by events while profiling */
+    for (int e = 0; e < numOps;) {
+      TravOperands o;
+      if (trav_operands(&ops[e], c, &o) != 0) return -1;
       hipEvent_t ev_a = nullptr, ev_b = nullptr;
       if (g_prof_on) {
         prof_begin(&ev_a, &ev_b);
-        hipEventRecord(ev_a, s);
+        (void)hipEventRecord(ev_a, s);
       }
-      const double *P = dev_pbuf + (long)e * PBLK;
-      double *x3 = dev_clv + (long)op->x3Slot * clvStride;
-      const double *x1 = nullptr, *x2 = nullptr;
-      const unsigned char *t1 = nullptr, *t2 = nullptr;
-      if (STATES == 2) {
-        /* binary: one per-entry kernel, its own grid and streaming rule */
-        if (op->tipCase == EXAML_INNER_INNER)
-          x1 = dev_clv + (long)op->x1Slot * clvStride;
-        else
-          t1 = dev_tips + (long)op->x1Slot * tipStride;
-        if (op->tipCase == EXAML_TIP_TIP)
-          t2 = dev_tips + (long)op->x2Slot * tipStride;
-        else
-          x2 = dev_clv + (long)op->x2Slot * clvStride;
-        rc = launch_newview_bin(op->tipCase, s, x1, x2, x3, P, dev_EV,
-                                dev_tipVec, t1, t2, dev_wgt, n, dev_inc + e);
-      } else
-      switch (op->tipCase) {
-      case EXAML_TIP_TIP:
-        t1 = dev_tips + (long)op->x1Slot * tipStride;
-        t2 = dev_tips + (long)op->x2Slot * tipStride;
-        if (STATES == 4)
-          if (nt)
-      hipLaunchKernelGGL((k_newview_dna_gamma<EXAML_TIP_TIP, true>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, P, dev_EV, dev_tipVec, t1, t2, dev_wgt, n, dev_inc + e);
-    else
-      hipLaunchKernelGGL((k_newview_dna_gamma<EXAML_TIP_TIP, false>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, P, dev_EV, dev_tipVec, t1, t2, dev_wgt, n, dev_inc + e);
-        else
-          if (nt)
-      if (g_fast_math)
-      hipLaunchKernelGGL((k_newview_prot_gamma<EXAML_TIP_TIP, true, true>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, P, dev_EV, dev_tipVec, t1, t2, dev_wgt, n, dev_inc + e);
-    else
-      hipLaunchKernelGGL((k_newview_prot_gamma<EXAML_TIP_TIP, true, false>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, P, dev_EV, dev_tipVec, t1, t2, dev_wgt, n, dev_inc + e);
-    else
-      if (g_fast_math)
-      hipLaunchKernelGGL((k_newview_prot_gamma<EXAML_TIP_TIP, false, true>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, P, dev_EV, dev_tipVec, t1, t2, dev_wgt, n, dev_inc + e);
-    else
-      hipLaunchKernelGGL((k_newview_prot_gamma<EXAML_TIP_TIP, false, false>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, P, dev_EV, dev_tipVec, t1, t2, dev_wgt, n, dev_inc + e);
-        break;
-      case EXAML_TIP_INNER:
-        t1 = dev_tips + (long)op->x1Slot * tipStride;
-        x2 = dev_clv + (long)op->x2Slot * clvStride;
-        if (STATES == 4)
-          if (nt)
-      hipLaunchKernelGGL((k_newview_dna_gamma<EXAML_TIP_INNER, true>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, P, dev_EV, dev_tipVec, t1, t2, dev_wgt, n, dev_inc + e);
-    else
-      hipLaunchKernelGGL((k_newview_dna_gamma<EXAML_TIP_INNER, false>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, P, dev_EV, dev_tipVec, t1, t2, dev_wgt, n, dev_inc + e);
-        else
-          if (nt)
-      if (g_fast_math)
-      hipLaunchKernelGGL((k_newview_prot_gamma<EXAML_TIP_INNER, true, true>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, P, dev_EV, dev_tipVec, t1, t2, dev_wgt, n, dev_inc + e);
-    else
-      hipLaunchKernelGGL((k_newview_prot_gamma<EXAML_TIP_INNER, true, false>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, P, dev_EV, dev_tipVec, t1, t2, dev_wgt, n, dev_inc + e);
-    else
-      if (g_fast_math)
-      hipLaunchKernelGGL((k_newview_prot_gamma<EXAML_TIP_INNER, false, true>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, P, dev_EV, dev_tipVec, t1, t2, dev_wgt, n, dev_inc + e);
-    else
-      hipLaunchKernelGGL((k_newview_prot_gamma<EXAML_TIP_INNER, false, false>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, P, dev_EV, dev_tipVec, t1, t2, dev_wgt, n, dev_inc + e);
-        break;
-      case EXAML_INNER_INNER:
-        x1 = dev_clv + (long)op->x1Slot * clvStride;
-        x2 = dev_clv + (long)op->x2Slot * clvStride;
-        if (STATES == 4)
-          if (nt)
-      hipLaunchKernelGGL((k_newview_dna_gamma<EXAML_INNER_INNER, true>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, P, dev_EV, dev_tipVec, t1, t2, dev_wgt, n, dev_inc + e);
-    else
-      hipLaunchKernelGGL((k_newview_dna_gamma<EXAML_INNER_INNER, false>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, P, dev_EV, dev_tipVec, t1, t2, dev_wgt, n, dev_inc + e);
-        else
-          if (nt)
-      if (g_fast_math)
-      hipLaunchKernelGGL((k_newview_prot_gamma<EXAML_INNER_INNER, true, true>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, P, dev_EV, dev_tipVec, t1, t2, dev_wgt, n, dev_inc + e);
-    else
-      hipLaunchKernelGGL((k_newview_prot_gamma<EXAML_INNER_INNER, true, false>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, P, dev_EV, dev_tipVec, t1, t2, dev_wgt, n, dev_inc + e);
-    else
-      if (g_fast_math)
-      hipLaunchKernelGGL((k_newview_prot_gamma<EXAML_INNER_INNER, false, true>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, P, dev_EV, dev_tipVec, t1, t2, dev_wgt, n, dev_inc + e);
-    else
-      hipLaunchKernelGGL((k_newview_prot_gamma<EXAML_INNER_INNER, false, false>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, P, dev_EV, dev_tipVec, t1, t2, dev_wgt, n, dev_inc + e);
-        break;
-      default:
-        snprintf(g_err, sizeof(g_err), "traversal: bad tipCase %d",
-                 op->tipCase);
-        rc = -1;
-        break;
-      }
-      if (rc == 0) {
-        err = hipGetLastError();
-        if (err != hipSuccess) { rc = set_err(err, "newview launch"); break; }
-      }
+      const int used = launch_entry(e, o);
+      if (used <= 0) return -1;
+      err = hipGetLastError();
+      if (err != hipSuccess) return trav_err(c, err, "newview launch");
       if (g_prof_on) {
-        hipEventRecord(ev_b, s);
-        g_prof_pend.push_back({ev_a, ev_b, op->tipCase});
+        (void)hipEventRecord(ev_b, s);
+        g_prof_pend.push_back({ev_a, ev_b, ops[e].tipCase});
         if (g_prof_pend.size() > 2048) prof_flush();
       }
+      e += used;
     }
-    if (rc != 0) break;
 
     /* 3. recursive scaler accumulation (newviewGenericSpecial.c:1503) */
-    for (int base = 0; base < numOps && rc == 0; base += FIN_CHUNK) {
+    for (int base = 0; base < numOps; base += FIN_CHUNK) {
       FinMeta m;
       m.count = (numOps - base < FIN_CHUNK) ? (numOps - base) : FIN_CHUNK;
       m.base = base;
@@ -2217,39 +2286,13 @@ static int traversal_impl(const examl_hip_trav_entry *ops, int numOps,
         m.q[e] = ops[base + e].qNumber;
         m.r[e] = ops[base + e].rNumber;
       }
-      hipLaunchKernelGGL(k_scaler_finalize, dim3(1), dim3(64), 0, s, m,
-                         dev_inc, dev_scalers);
+      hipLaunchKernelGGL(k_scaler_finalize, dim3(1), dim3(64), 0, s, m, c.inc,
+                         c.scalers);
       err = hipGetLastError();
-      if (err != hipSuccess) rc = set_err(err, "finalize launch");
+      if (err != hipSuccess) return trav_err(c, err, "finalize launch");
     }
-  } while (0);
-
-  if (capturing) {
-    hipGraph_t graph = nullptr;
-    hipError_t err = hipStreamEndCapture(s, &graph);
-    if (rc != 0) {
-      if (graph) hipGraphDestroy(graph);
-      return rc;
-    }
-    hipGraphExec_t exec = nullptr;
-    if (err == hipSuccess) {
-      err = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-      hipGraphDestroy(graph);
-    }
-    if (err != hipSuccess) {
-      /* the captured sequence never executed: disable graphs and run it
-       * for real */
-      (void)hipGetLastError();
-      g_use_graphs = false;
-      return traversal_impl<STATES>(ops, numOps, EIGN, EI, gammaRates,
-                                    dev_EV, dev_tipVec, dev_clv, clvStride,
-                                    dev_tips, tipStride, dev_wgt, n,
-                                    dev_scalers, dev_inc, dev_pbuf, s);
-    }
-    trav_graph_store(key, exec);
-    CHK(hipGraphLaunch(exec, s));
-  }
-  return rc;
+    return 0;
+  });
 }
 
 extern "C" int examl_hip_newview_traversal_dna_gamma(
@@ -2261,10 +2304,52 @@ extern "C" int examl_hip_newview_traversal_dna_gamma(
     void *stream) {
   if (numOps <= 0 || n <= 0) return 0;
   (void)hipGetLastError();
-  return traversal_impl<4>(ops, numOps, EIGN, EI, gammaRates, dev_EV,
-                           dev_tipVec, dev_clv, clvStride, dev_tips,
-                           tipStride, dev_wgt, n, dev_scalers, dev_inc,
-                           dev_pbuf, (hipStream_t)stream);
+  const TravCall c = {"traversal_dna_gamma", 4, 128, ops, numOps, dev_EV,
+                      dev_tipVec, nullptr, dev_clv, clvStride, dev_tips,
+                      tipStride, dev_wgt, n, dev_scalers, dev_inc, dev_pbuf,
+                      (hipStream_t)stream};
+  const bool nt = n >= 65536; /* streaming stores once x3 exceeds L2 */
+  /* runs of >= 2 ops the planner accepts go through the fused kernel;
+   * single-op launches, rejected lists and the HIP-event profiling mode
+   * keep the per-op kernel.  Planned at the first launch, so a graph
+   * replay, which launches nothing from here, never plans. */
+  std::vector<FusedPlanOp> plan;
+  std::vector<int> fused_len;
+  return run_traversal(
+      c, host_make_p(gammaRates, EI, EIGN, 4, 4),
+      [&](int e, const TravOperands &o) {
+        if (fused_len.empty()) {
+          fused_len.assign((size_t)numOps, 0);
+          if (g_use_fused && !g_prof_on &&
+              fused_plan(ops, numOps, FUSED_D, FUSED_MAX_OPS, plan) > 0)
+            for (int i = 0, len; i < numOps; i += len) {
+              len = 1;
+              while (i + len < numOps &&
+                     plan[(size_t)(i + len)].launch == plan[(size_t)i].launch)
+                len++;
+              fused_len[(size_t)i] = len;
+            }
+        }
+        const int len = fused_len[(size_t)e];
+        if (len < 2) {
+          launch_newview_dna_gamma(ops[e].tipCase, nt, c.stream, o.x1, o.x2,
+                                   o.x3, o.P, dev_EV, dev_tipVec, o.t1, o.t2,
+                                   dev_wgt, n, o.inc);
+          return 1;
+        }
+        FusedProg pg;
+        fused_build_prog(ops, plan, e, len, &pg);
+        const long tiles = (n + FUSED_SITES - 1) / FUSED_SITES;
+        const int fgrid =
+            (int)(tiles < FUSED_GRID_CAP ? tiles : FUSED_GRID_CAP);
+        with_flag(nt, [&](auto ntc) {
+          hipLaunchKernelGGL(
+              (k_newview_dna_gamma_fused<decltype(ntc)::value>), dim3(fgrid),
+              dim3(NV_BLOCK), 0, c.stream, pg, dev_clv, clvStride, dev_tips,
+              tipStride, dev_pbuf, dev_EV, dev_tipVec, dev_wgt, n, dev_inc);
+        });
+        return len;
+      });
 }
 
 /* --- evaluate at the root (evaluateIterative body) ------------------------ */
@@ -2321,27 +2406,13 @@ extern "C" int examl_hip_sum_root_dna_gamma(
     const double *dev_tipVec, double *dev_clv, long clvStride,
     const unsigned char *dev_tips, long tipStride, double *dev_sum, long n,
     void *stream) {
-  const double *x1 = nullptr, *x2 = nullptr;
-  const unsigned char *t1 = nullptr, *t2 = nullptr;
-  switch (rootTipCase) {
-  case EXAML_TIP_TIP:
-    t1 = dev_tips + (long)tipSlot * tipStride;
-    t2 = dev_tips + (long)tipSlot2 * tipStride;
-    break;
-  case EXAML_TIP_INNER:
-    t1 = dev_tips + (long)tipSlot * tipStride;
-    x2 = dev_clv + (long)x2Slot * clvStride;
-    break;
-  case EXAML_INNER_INNER:
-    x1 = dev_clv + (long)x1Slot * clvStride;
-    x2 = dev_clv + (long)x2Slot * clvStride;
-    break;
-  default:
-    snprintf(g_err, sizeof(g_err), "sum_root: bad tipCase %d", rootTipCase);
+  TravOperands o;
+  if (sum_root_operands(rootTipCase, x1Slot, x2Slot, tipSlot, tipSlot2,
+                        dev_clv, clvStride, dev_tips, tipStride, "sum_root",
+                        &o) != 0)
     return -1;
-  }
-  return examl_hip_sum_dna_gamma(rootTipCase, dev_sum, x1, x2, dev_tipVec, t1,
-                                 t2, n, stream);
+  return examl_hip_sum_dna_gamma(rootTipCase, dev_sum, o.x1, o.x2, dev_tipVec,
+                                 o.t1, o.t2, n, stream);
 }
 
 extern "C" int examl_hip_core_root_dna_gamma(long n, const double *dev_sum,
@@ -2376,10 +2447,18 @@ extern "C" int examl_hip_newview_traversal_bin_gamma(
     void *stream) {
   if (numOps <= 0 || n <= 0) return 0;
   (void)hipGetLastError();
-  return traversal_impl<2>(ops, numOps, EIGN, EI, gammaRates, dev_EV,
-                           dev_tipVec, dev_clv, clvStride, dev_tips,
-                           tipStride, dev_wgt, n, dev_scalers, dev_inc,
-                           dev_pbuf, (hipStream_t)stream);
+  const TravCall c = {"traversal_bin_gamma", 2, 32, ops, numOps, dev_EV,
+                      dev_tipVec, nullptr, dev_clv, clvStride, dev_tips,
+                      tipStride, dev_wgt, n, dev_scalers, dev_inc, dev_pbuf,
+                      (hipStream_t)stream};
+  return run_traversal(
+      c, host_make_p(gammaRates, EI, EIGN, 4, 2),
+      [&](int e, const TravOperands &o) {
+        /* its own grid and streaming rule */
+        return launch_newview_bin(ops[e].tipCase, c.stream, o.x1, o.x2, o.x3,
+                                  o.P, dev_EV, dev_tipVec, o.t1, o.t2,
+                                  dev_wgt, n, o.inc) == 0 ? 1 : 0;
+      });
 }
 
 extern "C" int examl_hip_evaluate_root_bin_gamma(
@@ -2421,28 +2500,13 @@ extern "C" int examl_hip_sum_root_bin_gamma(
     const double *dev_tipVec, double *dev_clv, long clvStride,
     const unsigned char *dev_tips, long tipStride, double *dev_sum, long n,
     void *stream) {
-  const double *x1 = nullptr, *x2 = nullptr;
-  const unsigned char *t1 = nullptr, *t2 = nullptr;
-  switch (rootTipCase) {
-  case EXAML_TIP_TIP:
-    t1 = dev_tips + (long)tipSlot * tipStride;
-    t2 = dev_tips + (long)tipSlot2 * tipStride;
-    break;
-  case EXAML_TIP_INNER:
-    t1 = dev_tips + (long)tipSlot * tipStride;
-    x2 = dev_clv + (long)x2Slot * clvStride;
-    break;
-  case EXAML_INNER_INNER:
-    x1 = dev_clv + (long)x1Slot * clvStride;
-    x2 = dev_clv + (long)x2Slot * clvStride;
-    break;
-  default:
-    snprintf(g_err, sizeof(g_err), "sum_root_bin: bad tipCase %d",
-             rootTipCase);
+  TravOperands o;
+  if (sum_root_operands(rootTipCase, x1Slot, x2Slot, tipSlot, tipSlot2,
+                        dev_clv, clvStride, dev_tips, tipStride,
+                        "sum_root_bin", &o) != 0)
     return -1;
-  }
-  return examl_hip_sum_bin_gamma(rootTipCase, dev_sum, x1, x2, dev_tipVec, t1,
-                                 t2, n, stream);
+  return examl_hip_sum_bin_gamma(rootTipCase, dev_sum, o.x1, o.x2, dev_tipVec,
+                                 o.t1, o.t2, n, stream);
 }
 
 extern "C" int examl_hip_core_root_bin_gamma(long n, const double *dev_sum,
@@ -2481,48 +2545,10 @@ extern "C" int examl_hip_newview_dna_cat(
              MAX_CAT);
     return -1;
   }
-  hipStream_t s = (hipStream_t)stream;
   (void)hipGetLastError();
-  const int grid = grid_for(n);
-  const bool nt = n >= 262144; /* 32 B/site write */
-  switch (tipCase) {
-  case EXAML_TIP_TIP:
-    if (nt)
-      hipLaunchKernelGGL((k_newview_dna_cat<EXAML_TIP_TIP, true>), dim3(grid),
-                         dim3(NV_BLOCK), 0, s, dev_EV, dev_cptr, x1, x2, x3,
-                         dev_tipVec, tipX1, tipX2, dev_wgt, n, dev_P, numCats,
-                         dev_scalerInc);
-    else
-      hipLaunchKernelGGL((k_newview_dna_cat<EXAML_TIP_TIP, false>),
-                         dim3(grid), dim3(NV_BLOCK), 0, s, dev_EV, dev_cptr,
-                         x1, x2, x3, dev_tipVec, tipX1, tipX2, dev_wgt, n,
-                         dev_P, numCats, dev_scalerInc);
-    break;
-  case EXAML_TIP_INNER:
-    if (nt)
-      hipLaunchKernelGGL((k_newview_dna_cat<EXAML_TIP_INNER, true>),
-                         dim3(grid), dim3(NV_BLOCK), 0, s, dev_EV, dev_cptr,
-                         x1, x2, x3, dev_tipVec, tipX1, tipX2, dev_wgt, n,
-                         dev_P, numCats, dev_scalerInc);
-    else
-      hipLaunchKernelGGL((k_newview_dna_cat<EXAML_TIP_INNER, false>),
-                         dim3(grid), dim3(NV_BLOCK), 0, s, dev_EV, dev_cptr,
-                         x1, x2, x3, dev_tipVec, tipX1, tipX2, dev_wgt, n,
-                         dev_P, numCats, dev_scalerInc);
-    break;
-  case EXAML_INNER_INNER:
-    if (nt)
-      hipLaunchKernelGGL((k_newview_dna_cat<EXAML_INNER_INNER, true>),
-                         dim3(grid), dim3(NV_BLOCK), 0, s, dev_EV, dev_cptr,
-                         x1, x2, x3, dev_tipVec, tipX1, tipX2, dev_wgt, n,
-                         dev_P, numCats, dev_scalerInc);
-    else
-      hipLaunchKernelGGL((k_newview_dna_cat<EXAML_INNER_INNER, false>),
-                         dim3(grid), dim3(NV_BLOCK), 0, s, dev_EV, dev_cptr,
-                         x1, x2, x3, dev_tipVec, tipX1, tipX2, dev_wgt, n,
-                         dev_P, numCats, dev_scalerInc);
-    break;
-  default:
+  if (!launch_newview_dna_cat(tipCase, (hipStream_t)stream, dev_EV, dev_cptr,
+                              x1, x2, x3, dev_tipVec, tipX1, tipX2, dev_wgt,
+                              n, dev_P, numCats, dev_scalerInc)) {
     snprintf(g_err, sizeof(g_err), "newview_cat: bad tipCase %d", tipCase);
     return -1;
   }
@@ -2638,153 +2664,20 @@ extern "C" int examl_hip_newview_traversal_dna_cat(
              MAX_CAT);
     return -1;
   }
-  hipStream_t s = (hipStream_t)stream;
   (void)hipGetLastError();
-  const int PBLK = numCats * 32; /* left|right, numCats categories */
-  HostPSlot *pslot = hostP_get(dev_pbuf, (size_t)numOps * PBLK);
-  double *hostP = pslot->buf;
-  for (int e = 0; e < numOps; e++) {
-    double qz = ops[e].qz, rz = ops[e].rz;
-    qz = (qz > ZMIN) ? log(qz) : log(ZMIN);
-    rz = (rz > ZMIN) ? log(rz) : log(ZMIN);
-    examl_host_make_p(qz, rz, perSiteRates, EI, EIGN, numCats,
-                      &hostP[e * PBLK], &hostP[e * PBLK + PBLK / 2], 4);
-  }
-
-  const bool want_graph =
-      g_use_graphs && !g_prof_on && s != nullptr && numOps >= 8;
-  unsigned long long key = 0;
-  bool capturing = false;
-  if (want_graph) {
-    key = trav_key(ops, numOps, n, dev_clv, dev_tips, dev_pbuf, dev_EV,
-                   dev_tipVec, dev_wgt, dev_scalers, dev_inc, (void *)s,
-                   1000 + numCats /* distinguish CAT shapes */);
-    hipGraphExec_t exec = trav_graph_find(key);
-    if (exec) {
-      CHK(hipGraphLaunch(exec, s));
-      return 0;
-    }
-    capturing =
-        hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) ==
-        hipSuccess;
-    (void)hipGetLastError();
-  }
-
-  int rc = 0;
-  do {
-    hipError_t err = hipMemcpyAsync(dev_pbuf, hostP,
-                                    (size_t)numOps * PBLK * sizeof(double),
-                                    hipMemcpyHostToDevice, s);
-    if (err != hipSuccess) { rc = set_err(err, "cat pbuf upload"); break; }
-    hipEventRecord(pslot->ev, s);
-    pslot->ev_valid = true;
-    err = hipMemsetAsync(dev_inc, 0, (size_t)numOps * sizeof(unsigned int),
-                         s);
-    if (err != hipSuccess) { rc = set_err(err, "cat inc memset"); break; }
-
-    const int grid = grid_for(n);
-    const bool nt = n >= 262144;
-    for (int e = 0; e < numOps && rc == 0; e++) {
-      const examl_hip_trav_entry *op = &ops[e];
-      const double *P = dev_pbuf + (long)e * PBLK;
-      double *x3 = dev_clv + (long)op->x3Slot * clvStride;
-      const double *x1 = nullptr, *x2 = nullptr;
-      const unsigned char *t1 = nullptr, *t2 = nullptr;
-      switch (op->tipCase) {
-      case EXAML_TIP_TIP:
-        t1 = dev_tips + (long)op->x1Slot * tipStride;
-        t2 = dev_tips + (long)op->x2Slot * tipStride;
-        if (nt)
-          hipLaunchKernelGGL((k_newview_dna_cat<EXAML_TIP_TIP, true>),
-                             dim3(grid), dim3(NV_BLOCK), 0, s, dev_EV,
-                             dev_cptr, x1, x2, x3, dev_tipVec, t1, t2,
-                             dev_wgt, n, P, numCats, dev_inc + e);
-        else
-          hipLaunchKernelGGL((k_newview_dna_cat<EXAML_TIP_TIP, false>),
-                             dim3(grid), dim3(NV_BLOCK), 0, s, dev_EV,
-                             dev_cptr, x1, x2, x3, dev_tipVec, t1, t2,
-                             dev_wgt, n, P, numCats, dev_inc + e);
-        break;
-      case EXAML_TIP_INNER:
-        t1 = dev_tips + (long)op->x1Slot * tipStride;
-        x2 = dev_clv + (long)op->x2Slot * clvStride;
-        if (nt)
-          hipLaunchKernelGGL((k_newview_dna_cat<EXAML_TIP_INNER, true>),
-                             dim3(grid), dim3(NV_BLOCK), 0, s, dev_EV,
-                             dev_cptr, x1, x2, x3, dev_tipVec, t1, t2,
-                             dev_wgt, n, P, numCats, dev_inc + e);
-        else
-          hipLaunchKernelGGL((k_newview_dna_cat<EXAML_TIP_INNER, false>),
-                             dim3(grid), dim3(NV_BLOCK), 0, s, dev_EV,
-                             dev_cptr, x1, x2, x3, dev_tipVec, t1, t2,
-                             dev_wgt, n, P, numCats, dev_inc + e);
-        break;
-      case EXAML_INNER_INNER:
-        x1 = dev_clv + (long)op->x1Slot * clvStride;
-        x2 = dev_clv + (long)op->x2Slot * clvStride;
-        if (nt)
-          hipLaunchKernelGGL((k_newview_dna_cat<EXAML_INNER_INNER, true>),
-                             dim3(grid), dim3(NV_BLOCK), 0, s, dev_EV,
-                             dev_cptr, x1, x2, x3, dev_tipVec, t1, t2,
-                             dev_wgt, n, P, numCats, dev_inc + e);
-        else
-          hipLaunchKernelGGL((k_newview_dna_cat<EXAML_INNER_INNER, false>),
-                             dim3(grid), dim3(NV_BLOCK), 0, s, dev_EV,
-                             dev_cptr, x1, x2, x3, dev_tipVec, t1, t2,
-                             dev_wgt, n, P, numCats, dev_inc + e);
-        break;
-      default:
-        snprintf(g_err, sizeof(g_err), "traversal_cat: bad tipCase %d",
-                 op->tipCase);
-        rc = -1;
-        break;
-      }
-      if (rc == 0) {
-        err = hipGetLastError();
-        if (err != hipSuccess) rc = set_err(err, "cat newview launch");
-      }
-    }
-    if (rc != 0) break;
-    for (int base = 0; base < numOps && rc == 0; base += FIN_CHUNK) {
-      FinMeta m;
-      m.count = (numOps - base < FIN_CHUNK) ? (numOps - base) : FIN_CHUNK;
-      m.base = base;
-      for (int e = 0; e < m.count; e++) {
-        m.p[e] = ops[base + e].pNumber;
-        m.q[e] = ops[base + e].qNumber;
-        m.r[e] = ops[base + e].rNumber;
-      }
-      hipLaunchKernelGGL(k_scaler_finalize, dim3(1), dim3(64), 0, s, m,
-                         dev_inc, dev_scalers);
-      err = hipGetLastError();
-      if (err != hipSuccess) rc = set_err(err, "cat finalize launch");
-    }
-  } while (0);
-
-  if (capturing) {
-    hipGraph_t graph = nullptr;
-    hipError_t err = hipStreamEndCapture(s, &graph);
-    if (rc != 0) {
-      if (graph) hipGraphDestroy(graph);
-      return rc;
-    }
-    hipGraphExec_t exec = nullptr;
-    if (err == hipSuccess) {
-      err = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-      hipGraphDestroy(graph);
-    }
-    if (err != hipSuccess) {
-      (void)hipGetLastError();
-      g_use_graphs = false;
-      return examl_hip_newview_traversal_dna_cat(
-          ops, numOps, EIGN, EI, perSiteRates, numCats, dev_EV, dev_tipVec,
-          dev_cptr, dev_clv, clvStride, dev_tips, tipStride, dev_wgt, n,
-          dev_scalers, dev_inc, dev_pbuf, (void *)s);
-    }
-    trav_graph_store(key, exec);
-    CHK(hipGraphLaunch(exec, s));
-  }
-  return rc;
+  /* P block: left|right, numCats categories */
+  const TravCall c = {"traversal_cat", 1000 + numCats, numCats * 32L, ops,
+                      numOps, dev_EV, dev_tipVec, dev_cptr, dev_clv,
+                      clvStride, dev_tips, tipStride, dev_wgt, n, dev_scalers,
+                      dev_inc, dev_pbuf, (hipStream_t)stream};
+  return run_traversal(
+      c, host_make_p(perSiteRates, EI, EIGN, numCats, 4),
+      [&](int e, const TravOperands &o) {
+        launch_newview_dna_cat(ops[e].tipCase, c.stream, dev_EV, dev_cptr,
+                               o.x1, o.x2, o.x3, dev_tipVec, o.t1, o.t2,
+                               dev_wgt, n, o.P, numCats, o.inc);
+        return 1;
+      });
 }
 
 extern "C" int examl_hip_evaluate_root_dna_cat_x(
@@ -2830,28 +2723,13 @@ extern "C" int examl_hip_sum_root_dna_cat(
     const double *dev_tipVec, double *dev_clv, long clvStride,
     const unsigned char *dev_tips, long tipStride, double *dev_sum, long n,
     void *stream) {
-  const double *x1 = nullptr, *x2 = nullptr;
-  const unsigned char *t1 = nullptr, *t2 = nullptr;
-  switch (rootTipCase) {
-  case EXAML_TIP_TIP:
-    t1 = dev_tips + (long)tipSlot * tipStride;
-    t2 = dev_tips + (long)tipSlot2 * tipStride;
-    break;
-  case EXAML_TIP_INNER:
-    t1 = dev_tips + (long)tipSlot * tipStride;
-    x2 = dev_clv + (long)x2Slot * clvStride;
-    break;
-  case EXAML_INNER_INNER:
-    x1 = dev_clv + (long)x1Slot * clvStride;
-    x2 = dev_clv + (long)x2Slot * clvStride;
-    break;
-  default:
-    snprintf(g_err, sizeof(g_err), "sum_root_cat: bad tipCase %d",
-             rootTipCase);
+  TravOperands o;
+  if (sum_root_operands(rootTipCase, x1Slot, x2Slot, tipSlot, tipSlot2,
+                        dev_clv, clvStride, dev_tips, tipStride,
+                        "sum_root_cat", &o) != 0)
     return -1;
-  }
-  return examl_hip_sum_dna_cat(rootTipCase, dev_sum, x1, x2, dev_tipVec, t1,
-                               t2, n, stream);
+  return examl_hip_sum_dna_cat(rootTipCase, dev_sum, o.x1, o.x2, dev_tipVec,
+                               o.t1, o.t2, n, stream);
 }
 
 /* ===========================================================================
@@ -2865,9 +2743,7 @@ extern "C" int examl_hip_newview_prot_gamma(
     const double *right, const int *wgt, unsigned int *scalerInc,
     void *stream) {
   if (n <= 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
   (void)hipGetLastError();
-  const int grid = grid_for(n * 8); /* two lanes per (site,cat) */
   const bool nt = false; /* NT hurts the protein kernel: its five strided
     32-B stores per thread defeat write-combining (measured 2x slower) */
   if (right != left + 1600) {
@@ -2875,44 +2751,9 @@ extern "C" int examl_hip_newview_prot_gamma(
              "newview_prot: right must be left+1600 (one P block)");
     return -1;
   }
-  switch (tipCase) {
-  case EXAML_TIP_TIP:
-    if (nt)
-      if (g_fast_math)
-      hipLaunchKernelGGL((k_newview_prot_gamma<EXAML_TIP_TIP, true, true>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, left, EV, tipVec, tipX1, tipX2, wgt, n, scalerInc);
-    else
-      hipLaunchKernelGGL((k_newview_prot_gamma<EXAML_TIP_TIP, true, false>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, left, EV, tipVec, tipX1, tipX2, wgt, n, scalerInc);
-    else
-      if (g_fast_math)
-      hipLaunchKernelGGL((k_newview_prot_gamma<EXAML_TIP_TIP, false, true>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, left, EV, tipVec, tipX1, tipX2, wgt, n, scalerInc);
-    else
-      hipLaunchKernelGGL((k_newview_prot_gamma<EXAML_TIP_TIP, false, false>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, left, EV, tipVec, tipX1, tipX2, wgt, n, scalerInc);
-    break;
-  case EXAML_TIP_INNER:
-    if (nt)
-      if (g_fast_math)
-      hipLaunchKernelGGL((k_newview_prot_gamma<EXAML_TIP_INNER, true, true>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, left, EV, tipVec, tipX1, tipX2, wgt, n, scalerInc);
-    else
-      hipLaunchKernelGGL((k_newview_prot_gamma<EXAML_TIP_INNER, true, false>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, left, EV, tipVec, tipX1, tipX2, wgt, n, scalerInc);
-    else
-      if (g_fast_math)
-      hipLaunchKernelGGL((k_newview_prot_gamma<EXAML_TIP_INNER, false, true>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, left, EV, tipVec, tipX1, tipX2, wgt, n, scalerInc);
-    else
-      hipLaunchKernelGGL((k_newview_prot_gamma<EXAML_TIP_INNER, false, false>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, left, EV, tipVec, tipX1, tipX2, wgt, n, scalerInc);
-    break;
-  case EXAML_INNER_INNER:
-    if (nt)
-      if (g_fast_math)
-      hipLaunchKernelGGL((k_newview_prot_gamma<EXAML_INNER_INNER, true, true>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, left, EV, tipVec, tipX1, tipX2, wgt, n, scalerInc);
-    else
-      hipLaunchKernelGGL((k_newview_prot_gamma<EXAML_INNER_INNER, true, false>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, left, EV, tipVec, tipX1, tipX2, wgt, n, scalerInc);
-    else
-      if (g_fast_math)
-      hipLaunchKernelGGL((k_newview_prot_gamma<EXAML_INNER_INNER, false, true>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, left, EV, tipVec, tipX1, tipX2, wgt, n, scalerInc);
-    else
-      hipLaunchKernelGGL((k_newview_prot_gamma<EXAML_INNER_INNER, false, false>), dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, left, EV, tipVec, tipX1, tipX2, wgt, n, scalerInc);
-    break;
-  default:
+  if (!launch_newview_prot_gamma(tipCase, nt, (hipStream_t)stream, x1, x2, x3,
+                                 left, EV, tipVec, tipX1, tipX2, wgt, n,
+                                 scalerInc)) {
     snprintf(g_err, sizeof(g_err), "newview_prot: bad tipCase %d", tipCase);
     return -1;
   }
@@ -3004,10 +2845,19 @@ extern "C" int examl_hip_newview_traversal_prot_gamma(
     void *stream) {
   if (numOps <= 0 || n <= 0) return 0;
   (void)hipGetLastError();
-  return traversal_impl<20>(ops, numOps, EIGN, EI, gammaRates, dev_EV,
-                            dev_tipVec, dev_clv, clvStride, dev_tips,
-                            tipStride, dev_wgt, n, dev_scalers, dev_inc,
-                            dev_pbuf, (hipStream_t)stream);
+  const TravCall c = {"traversal_prot_gamma", 20, 3200, ops, numOps, dev_EV,
+                      dev_tipVec, nullptr, dev_clv, clvStride, dev_tips,
+                      tipStride, dev_wgt, n, dev_scalers, dev_inc, dev_pbuf,
+                      (hipStream_t)stream};
+  return run_traversal(
+      c, host_make_p(gammaRates, EI, EIGN, 4, 20),
+      [&](int e, const TravOperands &o) {
+        /* no streaming stores: see examl_hip_newview_prot_gamma */
+        launch_newview_prot_gamma(ops[e].tipCase, false, c.stream, o.x1, o.x2,
+                                  o.x3, o.P, dev_EV, dev_tipVec, o.t1, o.t2,
+                                  dev_wgt, n, o.inc);
+        return 1;
+      });
 }
 
 extern "C" int examl_hip_evaluate_root_prot_gamma(
@@ -3057,28 +2907,13 @@ extern "C" int examl_hip_sum_root_prot_gamma(
     const double *dev_tipVec, double *dev_clv, long clvStride,
     const unsigned char *dev_tips, long tipStride, double *dev_sum, long n,
     void *stream) {
-  const double *x1 = nullptr, *x2 = nullptr;
-  const unsigned char *t1 = nullptr, *t2 = nullptr;
-  switch (rootTipCase) {
-  case EXAML_TIP_TIP:
-    t1 = dev_tips + (long)tipSlot * tipStride;
-    t2 = dev_tips + (long)tipSlot2 * tipStride;
-    break;
-  case EXAML_TIP_INNER:
-    t1 = dev_tips + (long)tipSlot * tipStride;
-    x2 = dev_clv + (long)x2Slot * clvStride;
-    break;
-  case EXAML_INNER_INNER:
-    x1 = dev_clv + (long)x1Slot * clvStride;
-    x2 = dev_clv + (long)x2Slot * clvStride;
-    break;
-  default:
-    snprintf(g_err, sizeof(g_err), "sum_root_prot: bad tipCase %d",
-             rootTipCase);
+  TravOperands o;
+  if (sum_root_operands(rootTipCase, x1Slot, x2Slot, tipSlot, tipSlot2,
+                        dev_clv, clvStride, dev_tips, tipStride,
+                        "sum_root_prot", &o) != 0)
     return -1;
-  }
-  return examl_hip_sum_prot_gamma(rootTipCase, dev_sum, x1, x2, dev_tipVec,
-                                  t1, t2, n, stream);
+  return examl_hip_sum_prot_gamma(rootTipCase, dev_sum, o.x1, o.x2,
+                                  dev_tipVec, o.t1, o.t2, n, stream);
 }
 
 extern "C" int examl_hip_core_root_prot_gamma(
@@ -3095,8 +2930,6 @@ extern "C" int examl_hip_core_root_prot_gamma(
   return examl_hip_core_prot_gamma(n, dev_sum, dev_dtab, dev_wgt,
                                    dev_partials, dev_out2, stream);
 }
-
-#undef CHK
 
 /* ===========================================================================
  * LG4 (LG4M/LG4X) protein kernels — one 20-state matrix per gamma category
@@ -3389,12 +3222,6 @@ __global__ __launch_bounds__(NV_BLOCK) void k_core_prot_lg4(
 
 /* ---- LG4 executors ------------------------------------------------------ */
 
-#define CHK(call)                                                              \
-  do {                                                                         \
-    hipError_t _e = (call);                                                    \
-    if (_e != hipSuccess) return set_err(_e, #call);                           \
-  } while (0)
-
 extern "C" void examl_host_make_p_lg4(double z1, double z2,
                                       const double *gammaRates,
                                       const double *EI4, const double *EIGN4,
@@ -3412,148 +3239,29 @@ extern "C" int examl_hip_newview_traversal_prot_lg4(
     const unsigned char *dev_tips, long tipStride, const int *dev_wgt, long n,
     unsigned int *dev_scalers, unsigned int *dev_inc, double *dev_pbuf,
     void *stream) {
+  if (numOps <= 0 || n <= 0) return 0;
   const examl_hip_trav_entry *ops = (const examl_hip_trav_entry *)ops_;
-  hipStream_t s = (hipStream_t)stream;
   (void)hipGetLastError();
-  constexpr int PBLK = 3200; /* 4 cats x 400 x {left,right} */
-  HostPSlot *pslot = hostP_get(dev_pbuf, (size_t)numOps * PBLK);
-  double *hostP = pslot->buf;
-  for (int e = 0; e < numOps; e++) {
-    double qz = ops[e].qz, rz = ops[e].rz;
-    qz = (qz > ZMIN) ? log(qz) : log(ZMIN);
-    rz = (rz > ZMIN) ? log(rz) : log(ZMIN);
-    examl_host_make_p_lg4(qz, rz, gammaRates, EI4, EIGN4, &hostP[e * PBLK],
-                          &hostP[e * PBLK + PBLK / 2]);
-  }
-
-  const bool want_graph =
-      g_use_graphs && !g_prof_on && s != nullptr && numOps >= 8;
-  unsigned long long key = 0;
-  bool capturing = false;
-  if (want_graph) {
-    key = trav_key(ops, numOps, n, dev_clv, dev_tips, dev_pbuf, dev_EV4,
-                   dev_tipVec4, dev_wgt, dev_scalers, dev_inc, (void *)s,
-                   2020 /* LG4 tag */);
-    hipGraphExec_t exec = trav_graph_find(key);
-    if (exec) {
-      CHK(hipGraphLaunch(exec, s));
-      return 0;
-    }
-    capturing =
-        hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) ==
-        hipSuccess;
-    (void)hipGetLastError();
-  }
-
-  int rc = 0;
-  do {
-    hipError_t err = hipMemcpyAsync(dev_pbuf, hostP,
-                                    (size_t)numOps * PBLK * sizeof(double),
-                                    hipMemcpyHostToDevice, s);
-    if (err != hipSuccess) { rc = set_err(err, "lg4 pbuf upload"); break; }
-    hipEventRecord(pslot->ev, s);
-    pslot->ev_valid = true;
-    err = hipMemsetAsync(dev_inc, 0, (size_t)numOps * sizeof(unsigned int),
-                         s);
-    if (err != hipSuccess) { rc = set_err(err, "lg4 inc memset"); break; }
-
-    const int grid = grid_for(n * 4);
-    for (int e = 0; e < numOps && rc == 0; e++) {
-      const examl_hip_trav_entry *op = &ops[e];
-      hipEvent_t ev_a = nullptr, ev_b = nullptr;
-      if (g_prof_on) {
-        prof_begin(&ev_a, &ev_b);
-        hipEventRecord(ev_a, s);
-      }
-      const double *P = dev_pbuf + (long)e * PBLK;
-      double *x3 = dev_clv + (long)op->x3Slot * clvStride;
-      const double *x1 = nullptr, *x2 = nullptr;
-      const unsigned char *t1 = nullptr, *t2 = nullptr;
-      switch (op->tipCase) {
-      case EXAML_TIP_TIP:
-        t1 = dev_tips + (long)op->x1Slot * tipStride;
-        t2 = dev_tips + (long)op->x2Slot * tipStride;
-        hipLaunchKernelGGL((k_newview_prot_lg4<EXAML_TIP_TIP, false>),
-                           dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, P,
-                           dev_EV4, dev_tipVec4, t1, t2, dev_wgt, n,
-                           dev_inc + e);
-        break;
-      case EXAML_TIP_INNER:
-        t1 = dev_tips + (long)op->x1Slot * tipStride;
-        x2 = dev_clv + (long)op->x2Slot * clvStride;
-        hipLaunchKernelGGL((k_newview_prot_lg4<EXAML_TIP_INNER, false>),
-                           dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, P,
-                           dev_EV4, dev_tipVec4, t1, t2, dev_wgt, n,
-                           dev_inc + e);
-        break;
-      case EXAML_INNER_INNER:
-        x1 = dev_clv + (long)op->x1Slot * clvStride;
-        x2 = dev_clv + (long)op->x2Slot * clvStride;
-        hipLaunchKernelGGL((k_newview_prot_lg4<EXAML_INNER_INNER, false>),
-                           dim3(grid), dim3(NV_BLOCK), 0, s, x1, x2, x3, P,
-                           dev_EV4, dev_tipVec4, t1, t2, dev_wgt, n,
-                           dev_inc + e);
-        break;
-      default:
-        snprintf(g_err, sizeof(g_err), "lg4 traversal: bad tipCase %d",
-                 op->tipCase);
-        rc = -1;
-        break;
-      }
-      if (rc == 0) {
-        err = hipGetLastError();
-        if (err != hipSuccess) { rc = set_err(err, "lg4 newview launch"); break; }
-      }
-      if (g_prof_on) {
-        hipEventRecord(ev_b, s);
-        g_prof_pend.push_back({ev_a, ev_b, op->tipCase});
-        if (g_prof_pend.size() > 2048) prof_flush();
-      }
-    }
-    if (rc != 0) break;
-
-    for (int base = 0; base < numOps && rc == 0; base += FIN_CHUNK) {
-      FinMeta m;
-      m.count = (numOps - base < FIN_CHUNK) ? (numOps - base) : FIN_CHUNK;
-      m.base = base;
-      for (int e = 0; e < m.count; e++) {
-        m.p[e] = ops[base + e].pNumber;
-        m.q[e] = ops[base + e].qNumber;
-        m.r[e] = ops[base + e].rNumber;
-      }
-      hipLaunchKernelGGL(k_scaler_finalize, dim3(1), dim3(64), 0, s, m,
-                         dev_inc, dev_scalers);
-      err = hipGetLastError();
-      if (err != hipSuccess) rc = set_err(err, "lg4 scaler finalize");
-    }
-  } while (0);
-
-  if (capturing) {
-    hipGraph_t graph = nullptr;
-    hipError_t err = hipStreamEndCapture(s, &graph);
-    if (rc != 0) {
-      if (graph) hipGraphDestroy(graph);
-      return rc;
-    }
-    hipGraphExec_t exec = nullptr;
-    if (err == hipSuccess) {
-      err = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-      hipGraphDestroy(graph);
-    }
-    if (err != hipSuccess) {
-      /* the captured sequence never executed: disable graphs and run it
-       * for real */
-      (void)hipGetLastError();
-      g_use_graphs = false;
-      return examl_hip_newview_traversal_prot_lg4(
-          ops_, numOps, EIGN4, EI4, gammaRates, dev_EV4, dev_tipVec4,
-          dev_clv, clvStride, dev_tips, tipStride, dev_wgt, n, dev_scalers,
-          dev_inc, dev_pbuf, stream);
-    }
-    trav_graph_store(key, exec);
-    CHK(hipGraphLaunch(exec, s));
-  }
-  return rc;
+  /* P block: 4 cats x 400 x {left,right} */
+  const TravCall c = {"traversal_prot_lg4", 2020, 3200, ops, numOps, dev_EV4,
+                      dev_tipVec4, nullptr, dev_clv, clvStride, dev_tips,
+                      tipStride, dev_wgt, n, dev_scalers, dev_inc, dev_pbuf,
+                      (hipStream_t)stream};
+  const int grid = grid_for(n * 4);
+  return run_traversal(
+      c,
+      [&](double qz, double rz, double *left, double *right) {
+        examl_host_make_p_lg4(qz, rz, gammaRates, EI4, EIGN4, left, right);
+      },
+      [&](int e, const TravOperands &o) {
+        with_tip_case(ops[e].tipCase, [&](auto tc) {
+          hipLaunchKernelGGL((k_newview_prot_lg4<decltype(tc)::value, false>),
+                             dim3(grid), dim3(NV_BLOCK), 0, c.stream, o.x1,
+                             o.x2, o.x3, o.P, dev_EV4, dev_tipVec4, o.t1,
+                             o.t2, dev_wgt, n, o.inc);
+        });
+        return 1;
+      });
 }
 
 extern "C" int examl_hip_evaluate_root_prot_lg4(
@@ -3606,36 +3314,17 @@ extern "C" int examl_hip_sum_root_prot_lg4(
     void *stream) {
   hipStream_t s = (hipStream_t)stream;
   (void)hipGetLastError();
-  const double *x1 = nullptr, *x2 = nullptr;
-  const unsigned char *t1 = nullptr, *t2 = nullptr;
-  const int grid = grid_for(n * 4);
-  switch (rootTipCase) {
-  case EXAML_TIP_TIP:
-    t1 = dev_tips + (long)tipSlot * tipStride;
-    t2 = dev_tips + (long)tipSlot2 * tipStride;
-    hipLaunchKernelGGL((k_sum_prot_lg4<EXAML_TIP_TIP>), dim3(grid),
-                       dim3(NV_BLOCK), 0, s, dev_sum, x1, x2, dev_tipVec4,
-                       t1, t2, n);
-    break;
-  case EXAML_TIP_INNER:
-    t1 = dev_tips + (long)tipSlot * tipStride;
-    x2 = dev_clv + (long)x2Slot * clvStride;
-    hipLaunchKernelGGL((k_sum_prot_lg4<EXAML_TIP_INNER>), dim3(grid),
-                       dim3(NV_BLOCK), 0, s, dev_sum, x1, x2, dev_tipVec4,
-                       t1, t2, n);
-    break;
-  case EXAML_INNER_INNER:
-    x1 = dev_clv + (long)x1Slot * clvStride;
-    x2 = dev_clv + (long)x2Slot * clvStride;
-    hipLaunchKernelGGL((k_sum_prot_lg4<EXAML_INNER_INNER>), dim3(grid),
-                       dim3(NV_BLOCK), 0, s, dev_sum, x1, x2, dev_tipVec4,
-                       t1, t2, n);
-    break;
-  default:
-    snprintf(g_err, sizeof(g_err), "sum_root_lg4: bad tipCase %d",
-             rootTipCase);
+  TravOperands o;
+  if (sum_root_operands(rootTipCase, x1Slot, x2Slot, tipSlot, tipSlot2,
+                        dev_clv, clvStride, dev_tips, tipStride,
+                        "sum_root_lg4", &o) != 0)
     return -1;
-  }
+  const int grid = grid_for(n * 4);
+  with_tip_case(rootTipCase, [&](auto tc) {
+    hipLaunchKernelGGL((k_sum_prot_lg4<decltype(tc)::value>), dim3(grid),
+                       dim3(NV_BLOCK), 0, s, dev_sum, o.x1, o.x2, dev_tipVec4,
+                       o.t1, o.t2, n);
+  });
   CHK(hipGetLastError());
   return 0;
 }
@@ -3662,8 +3351,6 @@ extern "C" int examl_hip_core_root_prot_lg4(
   CHK(hipGetLastError());
   return 0;
 }
-
-#undef CHK
 
 /* ===========================================================================
  * -S (saveMemory / SEV) DNA GTRGAMMA: gap-bit-compacted CLVs + per-node gap
@@ -3997,12 +3684,6 @@ __global__ __launch_bounds__(NV_BLOCK) void k_sum_dna_save(
   }
 }
 
-#define CHK(call)                                                              \
-  do {                                                                         \
-    hipError_t _e = (call);                                                    \
-    if (_e != hipSuccess) return set_err(_e, #call);                           \
-  } while (0)
-
 extern "C" int examl_hip_gap_and_prefix(const unsigned int *g1,
                                         const unsigned int *g2,
                                         unsigned int *g3, int *prefix,
@@ -4131,8 +3812,6 @@ extern "C" int examl_hip_sum_dna_save(
   CHK(hipGetLastError());
   return 0;
 }
-
-#undef CHK
 
 /* ===========================================================================
  * Protein CAT (PSR) kernels — span 20, per-site rate category.  newview in
@@ -4338,12 +4017,6 @@ __global__ __launch_bounds__(NV_BLOCK) void k_core_prot_cat(
   }
 }
 
-#define CHK(call)                                                              \
-  do {                                                                         \
-    hipError_t _e = (call);                                                    \
-    if (_e != hipSuccess) return set_err(_e, #call);                           \
-  } while (0)
-
 extern "C" void examl_host_core_dtables_prot_cat(const double *EIGN,
                                                  const double *rptr,
                                                  int numCats, double lz,
@@ -4362,143 +4035,25 @@ extern "C" int examl_hip_newview_traversal_prot_cat(
              numCats, MAX_CAT);
     return -1;
   }
-  hipStream_t s = (hipStream_t)stream;
   (void)hipGetLastError();
-  const long PBLK = (long)numCats * 800; /* left|right, numCats x 400 */
-  HostPSlot *pslot = hostP_get(dev_pbuf, (size_t)numOps * PBLK);
-  double *hostP = pslot->buf;
-  for (int e = 0; e < numOps; e++) {
-    double qz = ops[e].qz, rz = ops[e].rz;
-    qz = (qz > ZMIN) ? log(qz) : log(ZMIN);
-    rz = (rz > ZMIN) ? log(rz) : log(ZMIN);
-    examl_host_make_p(qz, rz, perSiteRates, EI, EIGN, numCats,
-                      &hostP[e * PBLK], &hostP[e * PBLK + PBLK / 2], 20);
-  }
-
-  const bool want_graph =
-      g_use_graphs && !g_prof_on && s != nullptr && numOps >= 8;
-  unsigned long long key = 0;
-  bool capturing = false;
-  if (want_graph) {
-    key = trav_key(ops, numOps, n, dev_clv, dev_tips, dev_pbuf, dev_EV,
-                   dev_tipVec, dev_wgt, dev_scalers, dev_inc, (void *)s,
-                   3000 + numCats /* prot CAT tag */);
-    hipGraphExec_t exec = trav_graph_find(key);
-    if (exec) {
-      CHK(hipGraphLaunch(exec, s));
-      return 0;
-    }
-    capturing =
-        hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) ==
-        hipSuccess;
-    (void)hipGetLastError();
-  }
-
-  int rc = 0;
-  do {
-    hipError_t err = hipMemcpyAsync(dev_pbuf, hostP,
-                                    (size_t)numOps * PBLK * sizeof(double),
-                                    hipMemcpyHostToDevice, s);
-    if (err != hipSuccess) { rc = set_err(err, "prot cat pbuf"); break; }
-    hipEventRecord(pslot->ev, s);
-    pslot->ev_valid = true;
-    err = hipMemsetAsync(dev_inc, 0, (size_t)numOps * sizeof(unsigned int),
-                         s);
-    if (err != hipSuccess) { rc = set_err(err, "prot cat inc"); break; }
-    const int grid = grid_for(n);
-    for (int e = 0; e < numOps && rc == 0; e++) {
-      const examl_hip_trav_entry *op = &ops[e];
-      hipEvent_t ev_a = nullptr, ev_b = nullptr;
-      if (g_prof_on) {
-        prof_begin(&ev_a, &ev_b);
-        hipEventRecord(ev_a, s);
-      }
-      const double *P = dev_pbuf + (long)e * PBLK;
-      double *x3 = dev_clv + (long)op->x3Slot * clvStride;
-      const double *x1 = nullptr, *x2 = nullptr;
-      const unsigned char *t1 = nullptr, *t2 = nullptr;
-      switch (op->tipCase) {
-      case EXAML_TIP_TIP:
-        t1 = dev_tips + (long)op->x1Slot * tipStride;
-        t2 = dev_tips + (long)op->x2Slot * tipStride;
-        hipLaunchKernelGGL((k_newview_prot_cat<EXAML_TIP_TIP>), dim3(grid),
-                           dim3(NV_BLOCK), 0, s, dev_EV, dev_cptr, x1, x2,
-                           x3, dev_tipVec, t1, t2, dev_wgt, n, P, numCats,
-                           dev_inc + e);
-        break;
-      case EXAML_TIP_INNER:
-        t1 = dev_tips + (long)op->x1Slot * tipStride;
-        x2 = dev_clv + (long)op->x2Slot * clvStride;
-        hipLaunchKernelGGL((k_newview_prot_cat<EXAML_TIP_INNER>), dim3(grid),
-                           dim3(NV_BLOCK), 0, s, dev_EV, dev_cptr, x1, x2,
-                           x3, dev_tipVec, t1, t2, dev_wgt, n, P, numCats,
-                           dev_inc + e);
-        break;
-      case EXAML_INNER_INNER:
-        x1 = dev_clv + (long)op->x1Slot * clvStride;
-        x2 = dev_clv + (long)op->x2Slot * clvStride;
-        hipLaunchKernelGGL((k_newview_prot_cat<EXAML_INNER_INNER>),
-                           dim3(grid), dim3(NV_BLOCK), 0, s, dev_EV,
-                           dev_cptr, x1, x2, x3, dev_tipVec, t1, t2,
-                           dev_wgt, n, P, numCats, dev_inc + e);
-        break;
-      default:
-        snprintf(g_err, sizeof(g_err), "prot cat traversal: bad tipCase %d",
-                 op->tipCase);
-        rc = -1;
-        break;
-      }
-      if (rc == 0) {
-        err = hipGetLastError();
-        if (err != hipSuccess) { rc = set_err(err, "prot cat launch"); break; }
-      }
-      if (g_prof_on) {
-        hipEventRecord(ev_b, s);
-        g_prof_pend.push_back({ev_a, ev_b, op->tipCase});
-        if (g_prof_pend.size() > 2048) prof_flush();
-      }
-    }
-    if (rc != 0) break;
-    for (int base = 0; base < numOps && rc == 0; base += FIN_CHUNK) {
-      FinMeta m;
-      m.count = (numOps - base < FIN_CHUNK) ? (numOps - base) : FIN_CHUNK;
-      m.base = base;
-      for (int e = 0; e < m.count; e++) {
-        m.p[e] = ops[base + e].pNumber;
-        m.q[e] = ops[base + e].qNumber;
-        m.r[e] = ops[base + e].rNumber;
-      }
-      hipLaunchKernelGGL(k_scaler_finalize, dim3(1), dim3(64), 0, s, m,
-                         dev_inc, dev_scalers);
-      err = hipGetLastError();
-      if (err != hipSuccess) rc = set_err(err, "prot cat finalize");
-    }
-  } while (0);
-
-  if (capturing) {
-    hipGraph_t graph = nullptr;
-    hipError_t err = hipStreamEndCapture(s, &graph);
-    if (rc != 0) {
-      if (graph) hipGraphDestroy(graph);
-      return rc;
-    }
-    hipGraphExec_t exec = nullptr;
-    if (err == hipSuccess) {
-      err = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-      hipGraphDestroy(graph);
-    }
-    if (err != hipSuccess) {
-      (void)hipGetLastError();
-      g_use_graphs = false;
-      return examl_hip_newview_traversal_prot_cat(
-          ops, numOps, EIGN, EI, perSiteRates, numCats, dev_EV, dev_tipVec,
-          dev_cptr, dev_clv, clvStride, dev_tips, tipStride, dev_wgt, n,
-          dev_scalers, dev_inc, dev_pbuf, stream);
-    }
-    trav_graph_store(key, exec);
-    CHK(hipGraphLaunch(exec, s));
-  }
-  return rc;
+  /* P block: left|right, numCats x 400 */
+  const TravCall c = {"traversal_prot_cat", 3000 + numCats,
+                      (long)numCats * 800, ops, numOps, dev_EV, dev_tipVec,
+                      dev_cptr, dev_clv, clvStride, dev_tips, tipStride,
+                      dev_wgt, n, dev_scalers, dev_inc, dev_pbuf,
+                      (hipStream_t)stream};
+  const int grid = grid_for(n);
+  return run_traversal(
+      c, host_make_p(perSiteRates, EI, EIGN, numCats, 20),
+      [&](int e, const TravOperands &o) {
+        with_tip_case(ops[e].tipCase, [&](auto tc) {
+          hipLaunchKernelGGL((k_newview_prot_cat<decltype(tc)::value>),
+                             dim3(grid), dim3(NV_BLOCK), 0, c.stream, dev_EV,
+                             dev_cptr, o.x1, o.x2, o.x3, dev_tipVec, o.t1,
+                             o.t2, dev_wgt, n, o.P, numCats, o.inc);
+        });
+        return 1;
+      });
 }
 
 extern "C" int examl_hip_evaluate_root_prot_cat(
@@ -4553,36 +4108,17 @@ extern "C" int examl_hip_sum_root_prot_cat(
     void *stream) {
   hipStream_t s = (hipStream_t)stream;
   (void)hipGetLastError();
-  const double *x1 = nullptr, *x2 = nullptr;
-  const unsigned char *t1 = nullptr, *t2 = nullptr;
-  const int grid = grid_for(n);
-  switch (rootTipCase) {
-  case EXAML_TIP_TIP:
-    t1 = dev_tips + (long)tipSlot * tipStride;
-    t2 = dev_tips + (long)tipSlot2 * tipStride;
-    hipLaunchKernelGGL((k_sum_prot_cat<EXAML_TIP_TIP>), dim3(grid),
-                       dim3(NV_BLOCK), 0, s, dev_sum, x1, x2, dev_tipVec,
-                       t1, t2, n);
-    break;
-  case EXAML_TIP_INNER:
-    t1 = dev_tips + (long)tipSlot * tipStride;
-    x2 = dev_clv + (long)x2Slot * clvStride;
-    hipLaunchKernelGGL((k_sum_prot_cat<EXAML_TIP_INNER>), dim3(grid),
-                       dim3(NV_BLOCK), 0, s, dev_sum, x1, x2, dev_tipVec,
-                       t1, t2, n);
-    break;
-  case EXAML_INNER_INNER:
-    x1 = dev_clv + (long)x1Slot * clvStride;
-    x2 = dev_clv + (long)x2Slot * clvStride;
-    hipLaunchKernelGGL((k_sum_prot_cat<EXAML_INNER_INNER>), dim3(grid),
-                       dim3(NV_BLOCK), 0, s, dev_sum, x1, x2, dev_tipVec,
-                       t1, t2, n);
-    break;
-  default:
-    snprintf(g_err, sizeof(g_err), "sum_root_prot_cat: bad tipCase %d",
-             rootTipCase);
+  TravOperands o;
+  if (sum_root_operands(rootTipCase, x1Slot, x2Slot, tipSlot, tipSlot2,
+                        dev_clv, clvStride, dev_tips, tipStride,
+                        "sum_root_prot_cat", &o) != 0)
     return -1;
-  }
+  const int grid = grid_for(n);
+  with_tip_case(rootTipCase, [&](auto tc) {
+    hipLaunchKernelGGL((k_sum_prot_cat<decltype(tc)::value>), dim3(grid),
+                       dim3(NV_BLOCK), 0, s, dev_sum, o.x1, o.x2, dev_tipVec,
+                       o.t1, o.t2, n);
+  });
   CHK(hipGetLastError());
   return 0;
 }
@@ -4616,8 +4152,6 @@ extern "C" int examl_hip_core_root_prot_cat(
   return 0;
 }
 
-#undef CHK
-
 /* ===========================================================================
  * Multi-partition fused executors ("mseg"): one kernel launch per
  * (traversal level x tipCase) covering ALL partitions, replacing the
@@ -4641,12 +4175,6 @@ extern "C" int examl_hip_core_root_prot_cat(
  * single-partition engines at <=1e-11 relative rather than bit-exact
  * (tests/test_multi_fused.py).
  * ==========================================================================*/
-
-#define CHK(call)                                                              \
-  do {                                                                         \
-    hipError_t _e = (call);                                                    \
-    if (_e != hipSuccess) return set_err(_e, #call);                           \
-  } while (0)
 
 struct MSeg { /* one (op, partition) newview work unit */
   const double *x1, *x2;
@@ -5914,171 +5442,137 @@ extern "C" int examl_hip_newview_traversal_multi(
   const double *d_active = h->d_stage + h->act_off;
 
   const bool want_graph = g_use_graphs && !g_prof_on && s != nullptr;
-  bool capturing = false;
-  if (want_graph) {
-    hipGraphExec_t exec = trav_graph_find(key);
-    if (exec) {
-      CHK(hipGraphLaunch(exec, s));
-      return 0;
-    }
-    capturing =
-        hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) ==
-        hipSuccess;
-    (void)hipGetLastError();
-  }
-
-  int rc = 0;
-  do {
-    hipError_t err =
-        hipMemcpyAsync(h->d_stage, st,
-                       ((size_t)numOps * NP * 2) * sizeof(double), /* zp */
-                       hipMemcpyHostToDevice, s);
-    if (err != hipSuccess) { rc = set_err(err, "zp upload"); break; }
-    err = hipMemcpyAsync(h->d_stage + h->mod_off, st + h->mod_off,
-                         ((size_t)NP * MSZ + NP) * sizeof(double),
+  return with_graph(key, want_graph, s, [&]() -> int {
+    int rc = 0;
+    do {
+      hipError_t err =
+          hipMemcpyAsync(h->d_stage, st,
+                         ((size_t)numOps * NP * 2) * sizeof(double), /* zp */
                          hipMemcpyHostToDevice, s);
-    if (err != hipSuccess) { rc = set_err(err, "mod upload"); break; }
-    hipEventRecord(slot->ev, s);
-    slot->ev_valid = true;
-    err = hipMemsetAsync(h->d_inc, 0,
-                         (size_t)numOps * NP * sizeof(unsigned int), s);
-    if (err != hipSuccess) { rc = set_err(err, "inc memset"); break; }
+      if (err != hipSuccess) { rc = set_err(err, "zp upload"); break; }
+      err = hipMemcpyAsync(h->d_stage + h->mod_off, st + h->mod_off,
+                           ((size_t)NP * MSZ + NP) * sizeof(double),
+                           hipMemcpyHostToDevice, s);
+      if (err != hipSuccess) { rc = set_err(err, "mod upload"); break; }
+      hipEventRecord(slot->ev, s);
+      slot->ev_valid = true;
+      err = hipMemsetAsync(h->d_inc, 0,
+                           (size_t)numOps * NP * sizeof(unsigned int), s);
+      if (err != hipSuccess) { rc = set_err(err, "inc memset"); break; }
 
-    if (S == 4)
-      hipLaunchKernelGGL((k_make_p_mseg<4>), dim3(numOps * NP), dim3(128),
-                         0, s, h->d_stage + h->zp_off,
-                         h->d_stage + h->mod_off, NP, h->d_pbuf);
-    else
-      hipLaunchKernelGGL((k_make_p_mseg<20>), dim3(numOps * NP), dim3(256),
-                         0, s, h->d_stage + h->zp_off,
-                         h->d_stage + h->mod_off, NP, h->d_pbuf);
-    err = hipGetLastError();
-    if (err != hipSuccess) { rc = set_err(err, "make_p launch"); break; }
+      if (S == 4)
+        hipLaunchKernelGGL((k_make_p_mseg<4>), dim3(numOps * NP), dim3(128),
+                           0, s, h->d_stage + h->zp_off,
+                           h->d_stage + h->mod_off, NP, h->d_pbuf);
+      else
+        hipLaunchKernelGGL((k_make_p_mseg<20>), dim3(numOps * NP), dim3(256),
+                           0, s, h->d_stage + h->zp_off,
+                           h->d_stage + h->mod_off, NP, h->d_pbuf);
+      err = hipGetLastError();
+      if (err != hipSuccess) { rc = set_err(err, "make_p launch"); break; }
 
 #define NV_MSEG(K) \
-  hipLaunchKernelGGL((K), dim3(g.grid), dim3(NV_BLOCK), 0, s, dsegs, db2s, \
-                     d_active)
-    if (fused) {
-      /* stream order carries the dependencies between launches */
-      const int fgrid =
-          h->numTiles < FUSED_GRID_CAP ? h->numTiles : FUSED_GRID_CAP;
-      for (auto &st : shape->fsteps) {
-        if (st.len >= 2) {
-          const FusedProg &pg = shape->progs[(size_t)st.idx];
-          /* bytes this launch stores: len CLVs of 16 doubles per site */
-          const int streamAll =
-              (long)st.len * h->totalSites * 128 > FUSED_STREAM_BYTES;
-          if (streamAll || h->anyWide)
-            hipLaunchKernelGGL((k_newview_dna_mseg_fused<true>), dim3(fgrid),
-                               dim3(NV_BLOCK), 0, s, pg, h->d_parts, NP,
-                               h->d_tilePart, h->d_tileSite0, h->numTiles,
-                               h->d_pbuf, h->d_inc, d_active, streamAll);
-          else
-            hipLaunchKernelGGL((k_newview_dna_mseg_fused<false>),
-                               dim3(fgrid), dim3(NV_BLOCK), 0, s, pg,
-                               h->d_parts, NP, h->d_tilePart, h->d_tileSite0,
-                               h->numTiles, h->d_pbuf, h->d_inc, d_active, 0);
-        } else {
-          const examl_hip_multi::Grp &g = shape->singles[(size_t)st.idx];
-          const MSeg *dsegs = shape->d_segs;
-          const int *db2s = shape->d_blk2seg + g.blkOff;
+    hipLaunchKernelGGL((K), dim3(g.grid), dim3(NV_BLOCK), 0, s, dsegs, db2s, \
+                       d_active)
+      if (fused) {
+        /* stream order carries the dependencies between launches */
+        const int fgrid =
+            h->numTiles < FUSED_GRID_CAP ? h->numTiles : FUSED_GRID_CAP;
+        for (auto &st : shape->fsteps) {
+          if (st.len >= 2) {
+            const FusedProg &pg = shape->progs[(size_t)st.idx];
+            /* bytes this launch stores: len CLVs of 16 doubles per site */
+            const int streamAll =
+                (long)st.len * h->totalSites * 128 > FUSED_STREAM_BYTES;
+            if (streamAll || h->anyWide)
+              hipLaunchKernelGGL((k_newview_dna_mseg_fused<true>), dim3(fgrid),
+                                 dim3(NV_BLOCK), 0, s, pg, h->d_parts, NP,
+                                 h->d_tilePart, h->d_tileSite0, h->numTiles,
+                                 h->d_pbuf, h->d_inc, d_active, streamAll);
+            else
+              hipLaunchKernelGGL((k_newview_dna_mseg_fused<false>),
+                                 dim3(fgrid), dim3(NV_BLOCK), 0, s, pg,
+                                 h->d_parts, NP, h->d_tilePart, h->d_tileSite0,
+                                 h->numTiles, h->d_pbuf, h->d_inc, d_active, 0);
+          } else {
+            const examl_hip_multi::Grp &g = shape->singles[(size_t)st.idx];
+            const MSeg *dsegs = shape->d_segs;
+            const int *db2s = shape->d_blk2seg + g.blkOff;
+            switch (g.tc) {
+            case EXAML_TIP_TIP: NV_MSEG(k_newview_dna_mseg<EXAML_TIP_TIP>); break;
+            case EXAML_TIP_INNER:
+              NV_MSEG(k_newview_dna_mseg<EXAML_TIP_INNER>); break;
+            default: NV_MSEG(k_newview_dna_mseg<EXAML_INNER_INNER>);
+            }
+          }
+          err = hipGetLastError();
+          if (err != hipSuccess) { rc = set_err(err, "fused mseg launch"); break; }
+        }
+      } else /* the level path: one launch per (level, tipCase) */
+      for (auto &g : shape->groups) {
+        hipEvent_t ev_a = nullptr, ev_b = nullptr;
+        if (g_prof_on) {
+          prof_begin(&ev_a, &ev_b);
+          hipEventRecord(ev_a, s);
+        }
+        const MSeg *dsegs = shape->d_segs;
+        const int *db2s = shape->d_blk2seg + g.blkOff;
+        if (S == 4) {
           switch (g.tc) {
           case EXAML_TIP_TIP: NV_MSEG(k_newview_dna_mseg<EXAML_TIP_TIP>); break;
           case EXAML_TIP_INNER:
             NV_MSEG(k_newview_dna_mseg<EXAML_TIP_INNER>); break;
           default: NV_MSEG(k_newview_dna_mseg<EXAML_INNER_INNER>);
           }
+        } else if (g_fast_math) {
+          switch (g.tc) {
+          case EXAML_TIP_TIP:
+            NV_MSEG((k_newview_prot_mseg<EXAML_TIP_TIP, true>)); break;
+          case EXAML_TIP_INNER:
+            NV_MSEG((k_newview_prot_mseg<EXAML_TIP_INNER, true>)); break;
+          default: NV_MSEG((k_newview_prot_mseg<EXAML_INNER_INNER, true>));
+          }
+        } else {
+          switch (g.tc) {
+          case EXAML_TIP_TIP:
+            NV_MSEG((k_newview_prot_mseg<EXAML_TIP_TIP, false>)); break;
+          case EXAML_TIP_INNER:
+            NV_MSEG((k_newview_prot_mseg<EXAML_TIP_INNER, false>)); break;
+          default: NV_MSEG((k_newview_prot_mseg<EXAML_INNER_INNER, false>));
+          }
         }
-        err = hipGetLastError();
-        if (err != hipSuccess) { rc = set_err(err, "fused mseg launch"); break; }
-      }
-    } else /* the level path: one launch per (level, tipCase) */
-    for (auto &g : shape->groups) {
-      hipEvent_t ev_a = nullptr, ev_b = nullptr;
-      if (g_prof_on) {
-        prof_begin(&ev_a, &ev_b);
-        hipEventRecord(ev_a, s);
-      }
-      const MSeg *dsegs = shape->d_segs;
-      const int *db2s = shape->d_blk2seg + g.blkOff;
-      if (S == 4) {
-        switch (g.tc) {
-        case EXAML_TIP_TIP: NV_MSEG(k_newview_dna_mseg<EXAML_TIP_TIP>); break;
-        case EXAML_TIP_INNER:
-          NV_MSEG(k_newview_dna_mseg<EXAML_TIP_INNER>); break;
-        default: NV_MSEG(k_newview_dna_mseg<EXAML_INNER_INNER>);
-        }
-      } else if (g_fast_math) {
-        switch (g.tc) {
-        case EXAML_TIP_TIP:
-          NV_MSEG((k_newview_prot_mseg<EXAML_TIP_TIP, true>)); break;
-        case EXAML_TIP_INNER:
-          NV_MSEG((k_newview_prot_mseg<EXAML_TIP_INNER, true>)); break;
-        default: NV_MSEG((k_newview_prot_mseg<EXAML_INNER_INNER, true>));
-        }
-      } else {
-        switch (g.tc) {
-        case EXAML_TIP_TIP:
-          NV_MSEG((k_newview_prot_mseg<EXAML_TIP_TIP, false>)); break;
-        case EXAML_TIP_INNER:
-          NV_MSEG((k_newview_prot_mseg<EXAML_TIP_INNER, false>)); break;
-        default: NV_MSEG((k_newview_prot_mseg<EXAML_INNER_INNER, false>));
-        }
-      }
 #undef NV_MSEG
-      err = hipGetLastError();
-      if (err != hipSuccess) { rc = set_err(err, "mseg launch"); break; }
-      if (g_prof_on) {
-        hipEventRecord(ev_b, s);
-        /* level-fused DNA groups (tc == -1) mix tipCases; bucket them
-         * under II — the P>1 roofline sums all buckets anyway */
-        g_prof_pend.push_back({ev_a, ev_b, g.tc < 0 ? 2 : g.tc});
-        if (g_prof_pend.size() > 2048) prof_flush();
+        err = hipGetLastError();
+        if (err != hipSuccess) { rc = set_err(err, "mseg launch"); break; }
+        if (g_prof_on) {
+          hipEventRecord(ev_b, s);
+          /* level-fused DNA groups (tc == -1) mix tipCases; bucket them
+           * under II — the P>1 roofline sums all buckets anyway */
+          g_prof_pend.push_back({ev_a, ev_b, g.tc < 0 ? 2 : g.tc});
+          if (g_prof_pend.size() > 2048) prof_flush();
+        }
       }
-    }
-    if (rc != 0) break;
+      if (rc != 0) break;
 
-    for (int base = 0; base < numOps && rc == 0; base += FIN_CHUNK) {
-      FinMetaL m;
-      m.count = (numOps - base < FIN_CHUNK) ? (numOps - base) : FIN_CHUNK;
-      m.base = base;
-      m.numLevels = shape->numLevels;
-      for (int e = 0; e < m.count; e++) {
-        m.p[e] = ops[base + e].pNumber;
-        m.q[e] = ops[base + e].qNumber;
-        m.r[e] = ops[base + e].rNumber;
-        m.lvl[e] = (short)shape->opLevel[base + e];
+      for (int base = 0; base < numOps && rc == 0; base += FIN_CHUNK) {
+        FinMetaL m;
+        m.count = (numOps - base < FIN_CHUNK) ? (numOps - base) : FIN_CHUNK;
+        m.base = base;
+        m.numLevels = shape->numLevels;
+        for (int e = 0; e < m.count; e++) {
+          m.p[e] = ops[base + e].pNumber;
+          m.q[e] = ops[base + e].qNumber;
+          m.r[e] = ops[base + e].rNumber;
+          m.lvl[e] = (short)shape->opLevel[base + e];
+        }
+        hipLaunchKernelGGL(k_scaler_finalize_mseg, dim3(NP), dim3(64), 0, s, m,
+                           h->d_inc, NP, h->d_gsArr, d_active);
+        err = hipGetLastError();
+        if (err != hipSuccess) rc = set_err(err, "finalize mseg");
       }
-      hipLaunchKernelGGL(k_scaler_finalize_mseg, dim3(NP), dim3(64), 0, s, m,
-                         h->d_inc, NP, h->d_gsArr, d_active);
-      err = hipGetLastError();
-      if (err != hipSuccess) rc = set_err(err, "finalize mseg");
-    }
-  } while (0);
-
-  if (capturing) {
-    hipGraph_t graph = nullptr;
-    hipError_t err = hipStreamEndCapture(s, &graph);
-    if (rc != 0) {
-      if (graph) hipGraphDestroy(graph);
-      return rc;
-    }
-    hipGraphExec_t exec = nullptr;
-    if (err == hipSuccess) {
-      err = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-      hipGraphDestroy(graph);
-    }
-    if (err != hipSuccess) {
-      (void)hipGetLastError();
-      g_use_graphs = false;
-      return examl_hip_newview_traversal_multi(vh, ops, numOps, EIGNs, EIs,
-                                               rates, activeMask, qzOv, rzOv,
-                                               stream);
-    }
-    trav_graph_store(key, exec);
-    CHK(hipGraphLaunch(exec, s));
-  }
-  return rc;
+    } while (0);
+    return rc;
+  });
 }
 
 extern "C" int examl_hip_evaluate_root_multi(

@@ -40,9 +40,11 @@ const char *examl_hip_version(void);
 const char *examl_hip_last_error_string(void);
 
 /* Kernel-time profiling for the bench's roofline leg: when enabled, every
- * newview launch of the traversal executor is bracketed with hipEvent pairs
- * on its launch stream; _get synchronizes outstanding pairs and returns the
- * accumulated {ms, launch count} per tipCase (index = EXAML_TIP_*). */
+ * newview launch of the traversal executors (all single-partition families,
+ * DNA CAT included, and the multi-partition level path) is bracketed with
+ * hipEvent pairs on its launch stream; _get synchronizes outstanding pairs
+ * and returns the accumulated {ms, launch count} per tipCase (index =
+ * EXAML_TIP_*). */
 void examl_hip_profile_enable(int on);
 void examl_hip_profile_reset(void);
 void examl_hip_profile_get(double *ms_by_tc, long *cnt_by_tc);
