@@ -726,6 +726,251 @@ __global__ __launch_bounds__(NV_BLOCK) void k_newview_dna_cat(
   }
 }
 
+/* --- fused CAT newview traversal -------------------------------------------
+ * The CAT form of k_newview_dna_gamma_fused: a run of traversal entries per
+ * tile of sites, each child CLV handed to its parent on chip (every x3 is
+ * still stored to the pool), operand sources MEM / REG / LDS resolved by
+ * the same planner and carried by the same FusedProg.
+ *
+ * What differs from GAMMA is the lane mapping and P.  One lane owns a whole
+ * site (its 4 doubles: one 32 B load or store), CATF_U sites per thread,
+ * NV_BLOCK sites apart, so every wave access is 2 KiB contiguous and a tile
+ * is CATF_U * NV_BLOCK sites.  The rescale verdict is thread-local (no
+ * ballot).  cptr[site] is loaded once per tile into a register, and the
+ * next tile's is prefetched during the tile's last entry.  P of an entry is
+ * numCats rows of left[16] | right[16]; the site's category picks the row,
+ * so there are no ump tables: tip rows come from sTV[4 * code] and go
+ * through the same product as an inner operand (k_newview_dna_cat's
+ * expressions, restated one for one: bit-identical results).
+ *
+ * P staging: rows are padded to CATF_PROW = 34 doubles, which spreads the
+ * 16-byte reads of lanes in different categories over 16 bank groups (a
+ * 32-double row pitch would put every category on the same two).  While
+ * entry k computes, each thread holds its at most 4 doubles of entry k+1's
+ * block (and that entry's tip codes) in registers and writes them to the
+ * other buffer after the arithmetic: ONE __syncthreads per entry.
+ *
+ * Barrier rules, as for the GAMMA kernel: the tile loop depends on
+ * blockIdx/gridDim only, the entry loop on prog.count only; lanes past n
+ * are predicated off (`active`) for loads, stores and atomics; no
+ * return/continue/break inside the loops.  The prefetch after a block's
+ * last tile reads entry 0's P block again (in range) and no site data.
+ */
+#ifndef CATF_U
+#define CATF_U 1 /* sites per thread and tile (1 beat 2: DESIGN §7g) */
+#endif
+#define CATF_SITES (CATF_U * NV_BLOCK) /* sites per tile */
+#ifndef CATF_PROW
+#define CATF_PROW 34 /* doubles per category row in LDS: left16|right16|pad */
+#endif
+
+template <bool NT>
+__global__ __launch_bounds__(NV_BLOCK) void k_newview_dna_cat_fused(
+    const FusedProg prog, double *__restrict__ clv, long clvStride,
+    const unsigned char *__restrict__ tips, long tipStride,
+    const double *__restrict__ pbuf, int pblk, const double *__restrict__ EV,
+    const double *__restrict__ tipVec, const int *__restrict__ cptr,
+    const int *__restrict__ wgt, long n, unsigned int *__restrict__ scalerInc) {
+  __shared__ double sEV[16], sTV[64];
+  __shared__ __attribute__((aligned(16))) double sP[2][MAX_CAT * CATF_PROW];
+  __shared__ v2d sStk[FUSED_D][CATF_U][2][NV_BLOCK];
+
+  const int tid = threadIdx.x;
+  const int count = prog.count;
+  const long tiles = (n + CATF_SITES - 1) / CATF_SITES;
+
+  /* this thread's (at most 4) doubles of a P block: source index tid +
+   * 256 k in left[numCats*16] | right[numCats*16], destination in the
+   * padded row layout; pd < 0 = none */
+  int pd[4];
+  {
+    const int half = pblk >> 1;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const int j = tid + k * NV_BLOCK;
+      const int side = j >= half;
+      const int jj = j - side * half;
+      pd[k] = j < pblk ? (jj >> 4) * CATF_PROW + side * 16 + (jj & 15) : -1;
+    }
+  }
+
+  if (tid < 64) sTV[tid] = tipVec[tid];
+  if (tid < 16) sEV[tid] = EV[tid];
+  /* stage entry 0 into buffer 0; tip codes and categories of the block's
+   * first tile */
+  {
+    const double *P = pbuf + (long)prog.base * pblk;
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      if (pd[k] >= 0) sP[0][pd[k]] = P[tid + k * NV_BLOCK];
+  }
+  int c1[CATF_U], c2[CATF_U], cat[CATF_U];
+  {
+    const int tc0 = (int)(prog.ctl[0] & 3u);
+#pragma unroll
+    for (int u = 0; u < CATF_U; u++) {
+      const long site0 = (long)blockIdx.x * CATF_SITES + u * NV_BLOCK + tid;
+      c1[u] = c2[u] = cat[u] = 0;
+      if (site0 < n) cat[u] = cptr[site0];
+      if (tc0 != EXAML_INNER_INNER && site0 < n)
+        c1[u] = tips[(long)prog.x1[0] * tipStride + site0];
+      if (tc0 == EXAML_TIP_TIP && site0 < n)
+        c2[u] = tips[(long)prog.x2[0] * tipStride + site0];
+    }
+  }
+  __syncthreads();
+
+  int buf = 0;
+  double r[CATF_U][4]; /* previous entry's result (REG) */
+#pragma unroll
+  for (int u = 0; u < CATF_U; u++) r[u][0] = r[u][1] = r[u][2] = r[u][3] = 0;
+
+  for (long t = blockIdx.x; t < tiles; t += gridDim.x) {
+    for (int e = 0; e < count; e++) {
+      const unsigned int ctl = prog.ctl[e];
+      const int tc = (int)(ctl & 3u);
+
+      /* ---- prefetch the next entry's P block and tip codes (after the
+       * last entry: entry 0 of this block's next tile, with that tile's
+       * categories; past the last tile every lane is inactive) ---- */
+      const bool last = e + 1 == count;
+      const int en = last ? 0 : e + 1;
+      const long tn = last ? t + gridDim.x : t;
+      const int tcn = (int)(prog.ctl[en] & 3u);
+      const double *Pn = pbuf + (long)(prog.base + en) * pblk;
+      double pn[4];
+      int c1n[CATF_U], c2n[CATF_U], catn[CATF_U];
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        pn[k] = 0;
+        if (pd[k] >= 0) pn[k] = Pn[tid + k * NV_BLOCK];
+      }
+#pragma unroll
+      for (int u = 0; u < CATF_U; u++) {
+        const long siten = tn * CATF_SITES + u * NV_BLOCK + tid;
+        c1n[u] = c2n[u] = catn[u] = 0;
+        if (last && siten < n) catn[u] = cptr[siten];
+        if (tcn != EXAML_INNER_INNER && siten < n)
+          c1n[u] = tips[(long)prog.x1[en] * tipStride + siten];
+        if (tcn == EXAML_TIP_TIP && siten < n)
+          c2n[u] = tips[(long)prog.x2[en] * tipStride + siten];
+      }
+
+      /* ---- entry e on this tile ---- */
+#pragma unroll
+      for (int u = 0; u < CATF_U; u++) {
+        const long site = t * CATF_SITES + u * NV_BLOCK + tid;
+        const bool active = site < n;
+        const double *le = &sP[buf][cat[u] * CATF_PROW];
+        const double *ri = le + 16;
+        double a[4], b[4];
+        if (tc == EXAML_TIP_TIP) {
+          const double *t1 = &sTV[4 * c1[u]];
+          const double *t2 = &sTV[4 * c2[u]];
+#pragma unroll
+          for (int s = 0; s < 4; s++) {
+            a[s] = t1[s];
+            b[s] = t2[s];
+          }
+        } else {
+          /* x2 is an inner operand in both remaining cases */
+          const unsigned int k2 = (ctl >> 4) & 3u;
+          if (k2 == FSRC_REG) {
+            b[0] = r[u][0]; b[1] = r[u][1]; b[2] = r[u][2]; b[3] = r[u][3];
+          } else if (k2 == FSRC_LDS) {
+            const int sl = (int)((ctl >> 10) & 15u);
+            const v2d lo = sStk[sl][u][0][tid], hi = sStk[sl][u][1][tid];
+            b[0] = lo.x; b[1] = lo.y; b[2] = hi.x; b[3] = hi.y;
+          } else {
+            double4 v = make_double4(0, 0, 0, 0);
+            if (active)
+              v = *reinterpret_cast<const double4 *>(
+                  &clv[(long)prog.x2[e] * clvStride + site * 4]);
+            b[0] = v.x; b[1] = v.y; b[2] = v.z; b[3] = v.w;
+          }
+          if (tc == EXAML_INNER_INNER) {
+            const unsigned int k1 = (ctl >> 2) & 3u;
+            if (k1 == FSRC_REG) {
+              a[0] = r[u][0]; a[1] = r[u][1]; a[2] = r[u][2]; a[3] = r[u][3];
+            } else if (k1 == FSRC_LDS) {
+              const int sl = (int)((ctl >> 6) & 15u);
+              const v2d lo = sStk[sl][u][0][tid], hi = sStk[sl][u][1][tid];
+              a[0] = lo.x; a[1] = lo.y; a[2] = hi.x; a[3] = hi.y;
+            } else {
+              double4 v = make_double4(0, 0, 0, 0);
+              if (active)
+                v = *reinterpret_cast<const double4 *>(
+                    &clv[(long)prog.x1[e] * clvStride + site * 4]);
+              a[0] = v.x; a[1] = v.y; a[2] = v.z; a[3] = v.w;
+            }
+          } else {
+            const double *t1 = &sTV[4 * c1[u]];
+            a[0] = t1[0]; a[1] = t1[1]; a[2] = t1[2]; a[3] = t1[3];
+          }
+        }
+
+        double v0 = 0, v1 = 0, v2 = 0, v3 = 0;
+#pragma unroll
+        for (int l = 0; l < 4; l++) {
+          const double u1 = (a[0] * le[l * 4] + a[1] * le[l * 4 + 1]) +
+                            (a[2] * le[l * 4 + 2] + a[3] * le[l * 4 + 3]);
+          const double u2 = (b[0] * ri[l * 4] + b[1] * ri[l * 4 + 1]) +
+                            (b[2] * ri[l * 4 + 2] + b[3] * ri[l * 4 + 3]);
+          const double tt = u1 * u2;
+          v0 += tt * sEV[l * 4 + 0];
+          v1 += tt * sEV[l * 4 + 1];
+          v2 += tt * sEV[l * 4 + 2];
+          v3 += tt * sEV[l * 4 + 3];
+        }
+
+        if (tc != EXAML_TIP_TIP) {
+          /* the site's whole span is in this lane: a thread-local verdict */
+          if (active & (fabs(v0) < MINLIKELIHOOD) &
+              (fabs(v1) < MINLIKELIHOOD) & (fabs(v2) < MINLIKELIHOOD) &
+              (fabs(v3) < MINLIKELIHOOD)) {
+            v0 *= TWOTOTHE256;
+            v1 *= TWOTOTHE256;
+            v2 *= TWOTOTHE256;
+            v3 *= TWOTOTHE256;
+            atomicAdd(scalerInc + prog.base + e, (unsigned int)wgt[site]);
+          }
+        }
+
+        if (active) {
+          double *x3 = &clv[(long)prog.x3[e] * clvStride + site * 4];
+          if (NT)
+            __builtin_nontemporal_store((v4d){v0, v1, v2, v3},
+                                        reinterpret_cast<v4d *>(x3));
+          else
+            *reinterpret_cast<double4 *>(x3) = make_double4(v0, v1, v2, v3);
+        }
+        if (ctl & (1u << 14)) {
+          const int sl = (int)((ctl >> 16) & 15u);
+          sStk[sl][u][0][tid] = (v2d){v0, v1};
+          sStk[sl][u][1][tid] = (v2d){v2, v3};
+        }
+        r[u][0] = v0; r[u][1] = v1; r[u][2] = v2; r[u][3] = v3;
+      }
+
+      /* ---- write the next entry's P block into the other buffer (last
+       * read by entry e-1, which every thread finished before the previous
+       * barrier) ---- */
+      const int nb = buf ^ 1;
+#pragma unroll
+      for (int k = 0; k < 4; k++)
+        if (pd[k] >= 0) sP[nb][pd[k]] = pn[k];
+#pragma unroll
+      for (int u = 0; u < CATF_U; u++) {
+        c1[u] = c1n[u];
+        c2[u] = c2n[u];
+        if (last) cat[u] = catn[u];
+      }
+      __syncthreads();
+      buf = nb;
+    }
+  }
+}
+
 /* evaluateGTRCAT (evaluateGenericSpecial.c:1988): per-site diag row,
  * no 0.25 factor */
 template <bool TIP>
@@ -1778,6 +2023,8 @@ struct TravGraph {
 static thread_local std::vector<TravGraph> g_graphs;
 static bool g_use_graphs = true;
 static bool g_use_fused = true;
+/* on-chip launches of this thread's last DNA CAT traversal call */
+static thread_local int g_cat_fused_launches = 0;
 
 extern "C" void examl_hip_fast_math(int on) { g_fast_math = on != 0; }
 
@@ -2658,6 +2905,7 @@ extern "C" int examl_hip_newview_traversal_dna_cat(
     double *dev_clv, long clvStride, const unsigned char *dev_tips,
     long tipStride, const int *dev_wgt, long n, unsigned int *dev_scalers,
     unsigned int *dev_inc, double *dev_pbuf, void *stream) {
+  g_cat_fused_launches = 0;
   if (numOps <= 0 || n <= 0) return 0;
   if (numCats > MAX_CAT) {
     snprintf(g_err, sizeof(g_err), "traversal_cat: numCats %d > %d", numCats,
@@ -2670,14 +2918,55 @@ extern "C" int examl_hip_newview_traversal_dna_cat(
                       numOps, dev_EV, dev_tipVec, dev_cptr, dev_clv,
                       clvStride, dev_tips, tipStride, dev_wgt, n, dev_scalers,
                       dev_inc, dev_pbuf, (hipStream_t)stream};
+  /* runs of >= 2 entries the planner accepts go through the on-chip
+   * kernel; single-entry launches, rejected lists, HIP-event profiling and
+   * examl_hip_use_fused(0) keep the per-entry kernel.  Planned once per
+   * call and before the graph shell, so that the launch count is that of
+   * this call's entry list on a replay too (a replayed graph was captured
+   * from the same list and the same switch: both are in its key). */
+  std::vector<FusedPlanOp> plan;
+  std::vector<int> fused_len((size_t)numOps, 0);
+  if (g_use_fused && !g_prof_on &&
+      fused_plan(ops, numOps, FUSED_D, FUSED_MAX_OPS, plan) > 0)
+    for (int i = 0, len; i < numOps; i += len) {
+      len = 1;
+      while (i + len < numOps &&
+             plan[(size_t)(i + len)].launch == plan[(size_t)i].launch)
+        len++;
+      fused_len[(size_t)i] = len;
+      if (len >= 2) g_cat_fused_launches++;
+    }
+  const bool nt = n >= 262144; /* launch_newview_dna_cat's rule */
   return run_traversal(
       c, host_make_p(perSiteRates, EI, EIGN, numCats, 4),
       [&](int e, const TravOperands &o) {
-        launch_newview_dna_cat(ops[e].tipCase, c.stream, dev_EV, dev_cptr,
-                               o.x1, o.x2, o.x3, dev_tipVec, o.t1, o.t2,
-                               dev_wgt, n, o.P, numCats, o.inc);
-        return 1;
+        const int len = fused_len[(size_t)e];
+        if (len < 2) {
+          launch_newview_dna_cat(ops[e].tipCase, c.stream, dev_EV, dev_cptr,
+                                 o.x1, o.x2, o.x3, dev_tipVec, o.t1, o.t2,
+                                 dev_wgt, n, o.P, numCats, o.inc);
+          return 1;
+        }
+        FusedProg pg;
+        fused_build_prog(ops, plan, e, len, &pg);
+        const long tiles = (n + CATF_SITES - 1) / CATF_SITES;
+        const int fgrid =
+            (int)(tiles < FUSED_GRID_CAP ? tiles : FUSED_GRID_CAP);
+        with_flag(nt, [&](auto ntc) {
+          hipLaunchKernelGGL(
+              (k_newview_dna_cat_fused<decltype(ntc)::value>), dim3(fgrid),
+              dim3(NV_BLOCK), 0, c.stream, pg, dev_clv, clvStride, dev_tips,
+              tipStride, dev_pbuf, numCats * 32, dev_EV, dev_tipVec, dev_cptr,
+              dev_wgt, n, dev_inc);
+        });
+        return len;
       });
+}
+
+extern "C" int examl_hip_cat_fused_tile_sites(void) { return CATF_SITES; }
+
+extern "C" int examl_hip_cat_fused_launches(void) {
+  return g_cat_fused_launches;
 }
 
 extern "C" int examl_hip_evaluate_root_dna_cat_x(

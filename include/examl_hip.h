@@ -315,6 +315,18 @@ int examl_hip_newview_traversal_dna_cat(
     unsigned int *dev_scalers, unsigned int *dev_inc, double *dev_pbuf,
     void *stream);
 
+/* On-chip DNA CAT traversal.  Like the GAMMA executor, the one above hands
+ * runs of at least 2 entries to one kernel that keeps each child CLV on
+ * chip for its parent (same planner, same examl_hip_use_fused switch, same
+ * exceptions; bit-identical CLVs and scaler counts).
+ * examl_hip_cat_fused_tile_sites: sites of one tile of that kernel; a launch
+ * uses at most examl_hip_fused_grid_cap() blocks, which stride over tiles.
+ * examl_hip_cat_fused_launches: on-chip launches of the calling thread's
+ * last examl_hip_newview_traversal_dna_cat call, graph replays included;
+ * 0 when the per-entry kernels ran. */
+int examl_hip_cat_fused_tile_sites(void);
+int examl_hip_cat_fused_launches(void);
+
 int examl_hip_evaluate_root_dna_cat_x(
     int rootTipCase, int pNumber, int qNumber, int x1Slot, int x2Slot,
     int tipSlot, double z, const double *EIGN, const double *perSiteRates,

@@ -1,0 +1,96 @@
+#!/usr/bin/env python3
+"""Step time of the DNA PSR (CAT) path: 50 taxa x 1,000,000 sites, 25 rate
+categories, the bench tree.  One step is DnaCatEngine.full_lnl: a full
+traversal (48 newview entries) plus the root evaluation.
+
+  python tools/cat_step_time.py --steps K --warmup W --fused 0|1
+
+--fused sets examl_hip_use_fused; on a build without the on-chip CAT kernel
+it changes nothing on this path.  Inputs are seeded and generated here.
+Prints ONE JSON line; lnl is printed with repr() precision so two builds
+can be compared digit for digit.  The time is a host clock around K steps
+that end in a device synchronise.
+"""
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+import examl_amd as ea  # noqa: E402
+from examl_amd.synthetic import make_alignment  # noqa: E402
+
+# traffic model of DESIGN §7g, bytes per site: II 32+32 in, 32 out, 4 cptr
+ENTRY_BYTES = {ea.TIP_TIP: 38, ea.TIP_INNER: 69, ea.INNER_INNER: 100}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=60)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--fused", type=int, choices=(0, 1), default=1)
+    ap.add_argument("--sites", type=int, default=1_000_000)
+    ap.add_argument("--taxa", type=int, default=50)
+    ap.add_argument("--cats", type=int, default=25)
+    args = ap.parse_args()
+
+    assert torch.cuda.is_available(), "cat_step_time needs a GPU"
+    L = ea.lib()
+    tips, wgt = make_alignment(args.taxa, args.sites, seed=42)
+    model = ea.DnaGtrModel([0.28, 0.22, 0.24, 0.26],
+                           [1.2, 2.9, 0.7, 1.0, 3.2, 1.0], alpha=0.6)
+    rates = np.linspace(0.05, 4.0, args.cats)
+    cptr = (np.arange(args.sites) % args.cats).astype(np.int32)
+    np.random.default_rng(1).shuffle(cptr)
+    tree = ea.PhyloTree.random(args.taxa, seed=7)
+    entries, _ = tree.full_traversal()
+    eng = ea.DnaCatEngine(tips, wgt, model, cptr, rates, device="cuda:0")
+
+    L.examl_hip_use_fused(args.fused)
+    try:
+        for _ in range(args.warmup):
+            lnl = eng.full_lnl(tree)
+        eng.sync()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            lnl = eng.full_lnl(tree)
+        eng.sync()
+        elapsed = time.perf_counter() - t0
+    finally:
+        L.examl_hip_use_fused(1)
+
+    # a build from before the on-chip CAT kernel has no launch counter
+    count = getattr(L, "examl_hip_cat_fused_launches", None)
+    launches = count() if count else 0
+    per_entry = sum(ENTRY_BYTES[e.tipCase] for e in entries)
+    ntip_reads = sum((e.tipCase != ea.INNER_INNER) + (e.tipCase == ea.TIP_TIP)
+                     for e in entries)
+    on_chip = 32 * len(entries) + ntip_reads + 4
+    ms = elapsed / args.steps * 1e3
+    model_bytes = (on_chip if launches else per_entry) * args.sites
+    print(json.dumps({
+        "metric": "DNA PSR full_lnl step time",
+        "ms_per_step": ms,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "fused": args.fused,
+        "on_chip_launches": launches,
+        "taxa": args.taxa,
+        "sites": args.sites,
+        "cats": args.cats,
+        "entries": len(entries),
+        "model_bytes_per_site": {"per_entry": per_entry, "on_chip": on_chip},
+        "model_tb_per_s": model_bytes / (ms * 1e-3) / 1e12,
+        "lnl": repr(float(lnl.item())),
+    }), flush=True)
+
+
+if __name__ == "__main__":
+    main()
