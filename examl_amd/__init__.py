@@ -207,6 +207,16 @@ def _bind(lib):
     lib.examl_hip_multi_use_fused.argtypes = [i]
     lib.examl_hip_multi_fused_launches.argtypes = [p]
     lib.examl_hip_multi_tile_table.argtypes = [p, i, i, p, p, i]
+    # on-chip multi-partition DNA PSR (CAT) traversal
+    lib.examl_hip_multi_cat_create.argtypes = \
+        [i, p, p, p, p, p, p, p, p, p, i, p]
+    lib.examl_hip_multi_cat_destroy.argtypes = [p]
+    lib.examl_hip_newview_traversal_multi_cat.argtypes = \
+        [p, p, i, p, p, p, p, p, p, p, p, p]
+    lib.examl_hip_multi_cat_fused_launches.argtypes = [p]
+    lib.examl_hip_multi_cat_plan.argtypes = [i, p, p, i, p, p]
+    lib.examl_hip_multi_cat_host_p_ms.argtypes = [p]
+    lib.examl_hip_multi_cat_host_p_ms.restype = d
     return lib
 
 
@@ -239,7 +249,8 @@ from .model import (BinGtrModel, DnaGtrModel, Lg4Model,  # noqa: E402
 from .tree import PhyloTree             # noqa: E402
 from .spr import SprSearch, SprTree     # noqa: E402
 from .engine import (DnaCatEngine, DnaGammaEngine, Lg4Engine,  # noqa: E402
-                     MultiDnaEngine, MultiEngine, ProtCatEngine, SaveCatEngine,
+                     MultiDnaCatEngine, MultiDnaEngine, MultiEngine,
+                     ProtCatEngine, SaveCatEngine,
                      SaveDnaEngine, SaveProtEngine)
 
 __all__ = [
@@ -247,7 +258,8 @@ __all__ = [
     "BinGtrModel",
     "Lg4Model", "PhyloTree", "SprSearch", "SprTree",
     "DnaGammaEngine", "DnaCatEngine", "Lg4Engine", "SaveDnaEngine",
-    "ProtCatEngine", "MultiDnaEngine", "MultiEngine", "SaveProtEngine",
+    "ProtCatEngine", "MultiDnaEngine", "MultiEngine", "MultiDnaCatEngine",
+    "SaveProtEngine",
     "SaveCatEngine",
     "TIP_TIP", "TIP_INNER",
     "INNER_INNER", "ZMIN", "ZMAX",

@@ -1953,6 +1953,7 @@ extern "C" int examl_hip_core_dna_gamma(long n, const double *sum,
  * traversal executor is bracketed by hipEvent pairs, accumulated per
  * tipCase on examl_hip_profile_get (which synchronizes the device).
  */
+#include <chrono>
 #include <vector>
 
 struct ProfEv {
@@ -5524,20 +5525,12 @@ static unsigned long long multi_graph_key(unsigned long long shapeKey,
                : shapeKey;
 }
 
-/* build (or fetch) the level/tipCase-grouped segment tables for one
- * traversal shape; segments and blk2seg live on the device, stable per
- * shape, so cached hipGraphs can bind them. */
-static examl_hip_multi::Shape *multi_shape_get(
-    examl_hip_multi *h, const examl_hip_trav_entry *ops, int numOps,
-    unsigned long long key, int *rc) {
-  *rc = 0;
-  for (auto &sh : h->shapes)
-    if (sh.key == key) return &sh;
-
-  const int PBLK = 8 * h->states * h->states;
-  /* dependency levels: an op must run after any earlier op that wrote a
-   * CLV slot it reads; same level = independent = one fused launch */
-  std::vector<int> level(numOps, 0);
+/* dependency levels: an op must run after any earlier op that wrote a
+ * CLV slot it reads; same level = independent = one fused launch (and one
+ * round of k_scaler_finalize_mseg).  -> the number of levels */
+static int trav_levels(const examl_hip_trav_entry *ops, int numOps,
+                       std::vector<int> &level) {
+  level.assign((size_t)numOps, 0);
   int maxSlot = 0;
   for (int e = 0; e < numOps; e++)
     if (ops[e].x3Slot > maxSlot) maxSlot = ops[e].x3Slot;
@@ -5557,6 +5550,22 @@ static examl_hip_multi::Shape *multi_shape_get(
   int numLevels = 0;
   for (int e = 0; e < numOps; e++)
     if (level[e] + 1 > numLevels) numLevels = level[e] + 1;
+  return numLevels;
+}
+
+/* build (or fetch) the level/tipCase-grouped segment tables for one
+ * traversal shape; segments and blk2seg live on the device, stable per
+ * shape, so cached hipGraphs can bind them. */
+static examl_hip_multi::Shape *multi_shape_get(
+    examl_hip_multi *h, const examl_hip_trav_entry *ops, int numOps,
+    unsigned long long key, int *rc) {
+  *rc = 0;
+  for (auto &sh : h->shapes)
+    if (sh.key == key) return &sh;
+
+  const int PBLK = 8 * h->states * h->states;
+  std::vector<int> level;
+  const int numLevels = trav_levels(ops, numOps, level);
 
   examl_hip_multi::Shape sh;
   sh.key = key;
@@ -5863,6 +5872,10 @@ extern "C" int examl_hip_newview_traversal_multi(
     return rc;
   });
 }
+
+/* on-chip DNA PSR (CAT) traversal over all partitions: kernel, executor and
+ * the examl_hip_multi_cat_* entry points */
+#include "examl_dna_cat_mseg.inc"
 
 extern "C" int examl_hip_evaluate_root_multi(
     void *vh, int rootTipCase, int pNumber, int qNumber, int x1Slot,

@@ -945,6 +945,94 @@ class MultiEngine:
         return z
 
 
+class MultiDnaCatEngine:
+    """On-chip DNA PSR (CAT) traversal over all partitions: one kernel per
+    planner launch instead of newviewIterative's partition loop
+    (newviewGenericSpecial.c:939).  Wraps per-partition DnaCatEngine
+    buffers; P blocks come from the host like the engines' own, so CLVs,
+    scaler counts and lnL are bit-identical to running each engine's
+    newview_traversal.  Evaluate, sum and core stay with the engines, which
+    read the same CLV pools."""
+
+    def __init__(self, engines):
+        assert engines and all(type(e) is DnaCatEngine for e in engines)
+        self.engines = engines
+        self.device = engines[0].device
+        NP = self.NP = len(engines)
+        self.max_ops = max(e._max_ops for e in engines)
+
+        def parr(vals):
+            return (ctypes.c_void_p * NP)(*vals)
+
+        def longs(vals):
+            return (ctypes.c_long * NP)(*vals)
+
+        h = ctypes.c_void_p()
+        check(lib().examl_hip_multi_cat_create(
+            NP, longs([e.width for e in engines]),
+            parr([e.d_clv.data_ptr() for e in engines]),
+            longs([e.width * 4 for e in engines]),
+            parr([e.d_tips.data_ptr() for e in engines]),
+            longs([e.width for e in engines]),
+            parr([e.d_wgt.data_ptr() for e in engines]),
+            parr([e.d_scalers.data_ptr() for e in engines]),
+            parr([e.d_EV.data_ptr() for e in engines]),
+            parr([e.d_tipVector.data_ptr() for e in engines]),
+            self.max_ops, ctypes.byref(h)), "multi_cat_create")
+        self.h = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                lib().examl_hip_multi_cat_destroy(self.h)
+        except Exception:
+            pass
+
+    def newview_traversal(self, entries, active=None, qz_ov=None,
+                          rz_ov=None):
+        """entries for every partition; active = executeModel mask; qz_ov /
+        rz_ov [len(entries), NP] = per-partition branch lengths (-M).  The
+        engines' category tensors, numCats and rates are read here, at every
+        call (set_site_rates replaces them)."""
+        if not entries:
+            return
+        assert len(entries) <= self.max_ops
+        NP, engs = self.NP, self.engines
+        arr = (TravEntry * len(entries))(*entries)
+
+        def dvec(v):
+            if v is None:
+                return None
+            a = np.ascontiguousarray(v, dtype=np.float64)
+            assert a.size == len(entries) * NP
+            return a
+
+        def hostp(arrays):
+            return (ctypes.c_void_p * NP)(*[a.ctypes.data for a in arrays])
+
+        qz_a, rz_a = dvec(qz_ov), dvec(rz_ov)
+        mask = None if active is None else \
+            (ctypes.c_ubyte * NP)(*[1 if a else 0 for a in active])
+        stream = ctypes.c_void_p(
+            torch.cuda.current_stream().cuda_stream
+            if self.device.type == "cuda" else 0)
+        check(lib().examl_hip_newview_traversal_multi_cat(
+            self.h, ctypes.cast(arr, ctypes.c_void_p), len(entries),
+            hostp([e.model.EIGN for e in engs]),
+            hostp([e.model.EI for e in engs]),
+            hostp([e.per_site_rates for e in engs]),
+            (ctypes.c_int * NP)(*[e.num_cats for e in engs]),
+            (ctypes.c_void_p * NP)(*[e.d_cptr.data_ptr() for e in engs]),
+            mask, _np_vp(qz_a) if qz_a is not None else None,
+            _np_vp(rz_a) if rz_a is not None else None, stream),
+            "newview_traversal_multi_cat")
+
+    def fused_launches(self):
+        """On-chip kernel launches of the last newview_traversal call (0
+        when it ran the per-partition loop)."""
+        return lib().examl_hip_multi_cat_fused_launches(self.h)
+
+
 class SaveProtEngine(SaveDnaEngine):
     """-S protein GTRGAMMA engine (span 80): the GPU side of the
     *_GAPPED_SAVE protein family (newviewGTRGAMMAPROT_AVX_GAPPED_SAVE,

@@ -100,6 +100,19 @@ class TreeSearch:
                 self.fused = MultiEngine(engines)
             except Exception:
                 self.fused = None
+        # partitioned DNA PSR: the traversal alone goes through one on-chip
+        # kernel over all partitions (MultiDnaCatEngine); evaluate, sum and
+        # core stay with the engines, which read the same CLV pools
+        self.fused_cat = None
+        if (self.M > 1 and rate_het == "CAT"
+                and all(type(e).__name__ == "DnaCatEngine" for e in engines)
+                and getattr(engines[0], "device", None) is not None
+                and engines[0].device.type == "cuda"):
+            try:
+                from .engine import MultiDnaCatEngine
+                self.fused_cat = MultiDnaCatEngine(engines)
+            except Exception:
+                self.fused_cat = None
 
     # ------------------------------------------------------------------
     # traversal construction (computeTraversalInfo,
@@ -224,16 +237,15 @@ class TreeSearch:
     def _run(self, entries):
         if not entries:
             return
-        if self.fused is not None:
+        multi = self.fused if self.fused is not None else self.fused_cat
+        if multi is not None:
             if self.NB == 1:
-                self.fused.newview_traversal(entries,
-                                             active=self.execute_model)
+                multi.newview_traversal(entries, active=self.execute_model)
             else:
                 qz = np.array([e.qzv[:self.NB] for e in entries])
                 rz = np.array([e.rzv[:self.NB] for e in entries])
-                self.fused.newview_traversal(entries,
-                                             active=self.execute_model,
-                                             qz_ov=qz, rz_ov=rz)
+                multi.newview_traversal(entries, active=self.execute_model,
+                                        qz_ov=qz, rz_ov=rz)
             return
         if self.NB == 1:
             for m, eng in enumerate(self.engines):

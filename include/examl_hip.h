@@ -783,6 +783,56 @@ int examl_hip_multi_tile_table(const long *widths, int numParts,
                                int tileSites, int *part_of_tile,
                                long *site0_of_tile, int cap);
 
+/* ---------------------------------------------------------------------------
+ * On-chip DNA PSR (CAT) traversal over all partitions: newviewIterative's
+ * partition loop (newviewGenericSpecial.c:939) around the GTRCAT case
+ * (newviewGTRCAT, :3002) as ONE kernel per planner launch, a one-entry launch
+ * included.  Tiles of examl_hip_cat_fused_tile_sites() sites come from
+ * examl_hip_multi_tile_table; child CLVs reach their parent on chip; every
+ * x3 is stored.
+ *
+ * examl_hip_multi_cat_create: binds the partitions' device buffers (a
+ * width-0 partition may pass null buffers) and sizes the P buffer for
+ * maxOps * numParts * 25 categories.
+ * examl_hip_newview_traversal_multi_cat: the P blocks are made on the host
+ * per (entry, partition) by examl_host_make_p (makeP, :78; branch lengths
+ * from qzOv/rzOv[numOps*numParts] when given, as under -M) and go up in one
+ * copy, so CLVs, scaler counts (:1503) and lnL are bit-identical to
+ * examl_hip_newview_traversal_dna_cat run per partition.  numCats and
+ * dev_cptrs are per-call operands (optimizeRateCategories replaces them,
+ * optimizeModel.c:2465).  activeMask is the executeModel gating; masked
+ * partitions are untouched.  Lists the planner rejects, HIP-event profiling
+ * and examl_hip_use_fused(0) / examl_hip_multi_use_fused(0) run the
+ * per-partition loop over the per-entry kernel, with the same results.
+ * numCats outside 1..25 on a partition with sites, numOps > maxOps or an
+ * unknown tipCase is refused before anything runs.
+ * examl_hip_multi_cat_fused_launches: on-chip launches of the last call on
+ * h, issued or replayed from its graph; 0 when it ran the loop.
+ * examl_hip_multi_cat_plan: the P-row geometry of a call, plain host code:
+ * catOff[p] = categories of the partitions with sites in front of p, *pRow =
+ * 32 * their total = doubles per entry; -1 for a malformed list.
+ * ------------------------------------------------------------------------ */
+int examl_hip_multi_cat_create(
+    int numParts, const long *widths, double *const *dev_clvs,
+    const long *clvStrides, const unsigned char *const *dev_tips,
+    const long *tipStrides, const int *const *dev_wgts,
+    unsigned int *const *dev_scalers, const double *const *dev_EVs,
+    const double *const *dev_tipVecs, int maxOps, void **out);
+void examl_hip_multi_cat_destroy(void *h);
+int examl_hip_newview_traversal_multi_cat(
+    void *h, const examl_hip_trav_entry *ops, int numOps,
+    const double *const *EIGNs, const double *const *EIs,
+    const double *const *perSiteRates, const int *numCats,
+    const int *const *dev_cptrs, const unsigned char *activeMask,
+    const double *qzOv, const double *rzOv, void *stream);
+int examl_hip_multi_cat_fused_launches(void *h);
+/* host milliseconds the last call on h spent making its P blocks (a steady
+ * clock around the examl_host_make_p loop; the upload is asynchronous) */
+double examl_hip_multi_cat_host_p_ms(void *h);
+int examl_hip_multi_cat_plan(int numParts, const long *widths,
+                             const int *numCats, int maxCat, int *catOff,
+                             long *pRow);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,9 +4,20 @@ categories, the bench tree.  One step is DnaCatEngine.full_lnl: a full
 traversal (48 newview entries) plus the root evaluation.
 
   python tools/cat_step_time.py --steps K --warmup W --fused 0|1
+                                [--partitions N] [--entries E]
 
 --fused sets examl_hip_use_fused; on a build without the on-chip CAT kernel
 it changes nothing on this path.  Inputs are seeded and generated here.
+--partitions N splits the sites equally into N partitions with one category
+set each; a step is then one traversal of all partitions (through
+MultiDnaCatEngine where the build has it, else the loop over the engines)
+plus the root evaluation of every partition and ONE synchronise.  --entries
+E times a partial traversal instead: the last E entries of the list, after
+one full traversal.  With partitions, host_p_ms is the executor's own host
+timer around the make_p loop of the last step
+(examl_hip_multi_cat_host_p_ms; null on a build without it) and upload_ms
+the time of one pinned copy of one step's P bytes, made and synchronised
+here.
 Prints ONE JSON line; lnl is printed with repr() precision so two builds
 can be compared digit for digit.  The time is a host clock around K steps
 that end in a device synchronise.
@@ -31,6 +42,94 @@ from examl_amd.synthetic import make_alignment  # noqa: E402
 ENTRY_BYTES = {ea.TIP_TIP: 38, ea.TIP_INNER: 69, ea.INNER_INNER: 100}
 
 
+def upload_ms(engs, entries):
+    """ms of one pinned, synchronised copy of one step's P blocks."""
+    src = torch.empty(len(entries) * sum(e.num_cats for e in engs) * 32,
+                      dtype=torch.float64).pin_memory()
+    dst = torch.empty_like(src, device="cuda:0")
+    dst.copy_(src, non_blocking=True)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(10):
+        dst.copy_(src, non_blocking=True)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e2
+
+
+def partitioned(args):
+    assert torch.cuda.is_available(), "cat_step_time needs a GPU"
+    L = ea.lib()
+    NP = args.partitions
+    tips, wgt = make_alignment(args.taxa, args.sites, seed=42)
+    tree = ea.PhyloTree.random(args.taxa, seed=7)
+    entries, (p, q, z) = tree.full_traversal()
+    cut = np.linspace(0, args.sites, NP + 1).astype(int)
+    engs = []
+    for i in range(NP):
+        w = int(cut[i + 1] - cut[i])
+        rng = np.random.default_rng(100 + i)
+        freqs = rng.uniform(0.2, 0.3, 4)
+        model = ea.DnaGtrModel(list(freqs / freqs.sum()),
+                               list(rng.uniform(0.5, 3.0, 5)) + [1.0],
+                               alpha=0.6)
+        cptr = (np.arange(w) % args.cats).astype(np.int32)
+        rng.shuffle(cptr)
+        engs.append(ea.DnaCatEngine(
+            np.ascontiguousarray(tips[:, cut[i]:cut[i + 1]]),
+            wgt[cut[i]:cut[i + 1]], model, cptr,
+            np.linspace(0.05, 4.0, args.cats) * (1 + 0.01 * i),
+            device="cuda:0"))
+    cls = getattr(ea, "MultiDnaCatEngine", None)
+    multi = cls(engs) if cls else None
+    timed = entries[-args.entries:] if args.entries else entries
+
+    def traverse(lst):
+        if multi is not None:
+            multi.newview_traversal(lst)
+        else:
+            for e in engs:
+                e.newview_traversal(lst)
+
+    def step():
+        traverse(timed)
+        return [e.evaluate_root(tree, p, q, z) for e in engs]
+
+    L.examl_hip_use_fused(args.fused)
+    try:
+        traverse(entries)
+        for _ in range(args.warmup):
+            outs = step()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            outs = step()
+        torch.cuda.synchronize()
+        elapsed = time.perf_counter() - t0
+    finally:
+        L.examl_hip_use_fused(1)
+    launches = multi.fused_launches() if multi is not None else 0
+    timer = getattr(L, "examl_hip_multi_cat_host_p_ms", None)
+    make_ms = timer(multi.h) if timer and multi is not None else None
+    up_ms = upload_ms(engs, timed)
+    print(json.dumps({
+        "metric": "partitioned DNA PSR step time",
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "fused": args.fused,
+        "multi_engine": multi is not None,
+        "on_chip_launches": launches,
+        "taxa": args.taxa,
+        "sites": args.sites,
+        "partitions": NP,
+        "cats": args.cats,
+        "entries": len(timed),
+        "host_p_ms": make_ms,
+        "upload_ms": up_ms,
+        "lnl": repr(float(sum(o.item() for o in outs))),
+    }), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=60)
@@ -39,7 +138,11 @@ def main():
     ap.add_argument("--sites", type=int, default=1_000_000)
     ap.add_argument("--taxa", type=int, default=50)
     ap.add_argument("--cats", type=int, default=25)
+    ap.add_argument("--partitions", type=int, default=1)
+    ap.add_argument("--entries", type=int, default=0)
     args = ap.parse_args()
+    if args.partitions > 1:
+        return partitioned(args)
 
     assert torch.cuda.is_available(), "cat_step_time needs a GPU"
     L = ea.lib()
