@@ -217,6 +217,17 @@ def _bind(lib):
     lib.examl_hip_multi_cat_plan.argtypes = [i, p, p, i, p, p]
     lib.examl_hip_multi_cat_host_p_ms.argtypes = [p]
     lib.examl_hip_multi_cat_host_p_ms.restype = d
+    # evaluate / sum / core of partitioned DNA PSR over all partitions
+    lib.examl_hip_evaluate_root_multi_cat.argtypes = \
+        [p, i, i, i, i, i, i, p, p, p, p, p, p, p, p]
+    lib.examl_hip_sum_root_multi_cat.argtypes = \
+        [p, i, i, i, i, i, p, p, p, p, p]
+    lib.examl_hip_core_root_multi_cat.argtypes = \
+        [p, p, p, p, p, p, p, p, p, p]
+    lib.examl_hip_multi_cat_root_kernels.argtypes = [p]
+    lib.examl_hip_multi_cat_root_units.argtypes = [i, p, p, p, l]
+    lib.examl_hip_multi_cat_root_units.restype = l
+    lib.examl_hip_multi_cat_root_grid_cap.argtypes = []
     return lib
 
 

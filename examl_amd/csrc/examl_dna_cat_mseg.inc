@@ -316,6 +316,300 @@ __global__ void k_clear_u32(unsigned int *__restrict__ p, long n) {
 }
 
 /* ---------------------------------------------------------------------------
+ * Root operations over ALL partitions: evaluate, sum and core of the DNA CAT
+ * family as one kernel per call plus one reduction block per partition
+ * (evaluateIterative / makenewzIterative / execCore partition loops,
+ * evaluateGenericSpecial.c:403, makenewzGenericSpecial.c:885).
+ *
+ * Unit of work = (partition p, virtual block b).  Partition p of n_p sites
+ * owns g_p = grid_for(n_p) consecutive units, the very grid its own engine
+ * launches; a width-0 partition owns none.  The launch has sum(g_p) blocks;
+ * block u reads p = unitPart[u] and b = u - unitPrefix[p] (two dependent
+ * scalar loads) and runs the per-engine kernel's loop
+ *   i = b * 256 + tid;  i < n_p;  i += g_p * 256
+ * with the per-engine kernel's expressions, shuffle ladder and 4-wave add,
+ * so partials[u] holds what block b of the engine's own launch would have
+ * written and the reduction adds the same g_p numbers in the same order:
+ * bit-identical by construction, wrapping partitions included.
+ *
+ * Barrier rules: the unit, and with it every loop bound and the early exit
+ * of a masked partition, depend on blockIdx, the unit tables and the active
+ * flags only.  A masked block returns before the first barrier and forms no
+ * address of its partition; every thread of a live block reaches every
+ * barrier; lanes past n_p run no loop iteration, so they load and store
+ * nothing.
+ *
+ * Tables (host-made, libm exp) sit at tabs + p * CATR_TAB: numCats x 4 diag
+ * doubles for evaluate, d[numCats x 4] | e1[4] | e2[4] | rptr[numCats] for
+ * core.  LDS rows keep the 32-byte pitch of the per-engine kernels.
+ * ------------------------------------------------------------------------ */
+
+#define CATR_TAB (MAX_CAT * 4 + 8 + MAX_CAT) /* table doubles per partition */
+
+struct CatrUnit {
+  int p, b, g;
+};
+
+__device__ __forceinline__ CatrUnit catr_unit(
+    const int *__restrict__ unitPart, const int *__restrict__ unitPrefix) {
+  CatrUnit u;
+  u.p = unitPart[blockIdx.x];
+  const int u0 = unitPrefix[u.p];
+  u.g = unitPrefix[u.p + 1] - u0;
+  u.b = (int)blockIdx.x - u0;
+  return u;
+}
+
+/* k_evaluate_dna_cat over all partitions */
+template <bool TIP>
+__global__ __launch_bounds__(NV_BLOCK) CATM_NO_PK_F32 void
+k_evaluate_dna_cat_mseg(const MCatDesc *__restrict__ parts,
+                        const int *__restrict__ unitPart,
+                        const int *__restrict__ unitPrefix,
+                        const double *__restrict__ active,
+                        const double *__restrict__ tabs, int x1Slot,
+                        int x2Slot, int tipSlot,
+                        double *__restrict__ partials) {
+  const CatrUnit u = catr_unit(unitPart, unitPrefix);
+  if (active[u.p] == 0.0) return;
+  __shared__ double sD[MAX_CAT * 4], sTV[TIP ? 64 : 1], sRed[NV_BLOCK / 64];
+  const MCatDesc d = parts[u.p];
+  const double *__restrict__ diag = tabs + (long)u.p * CATR_TAB;
+  const int tid = threadIdx.x;
+  for (int j = tid; j < d.numCats * 4; j += NV_BLOCK) sD[j] = diag[j];
+  if (TIP && tid < 64) sTV[tid] = d.tipVec[tid];
+  __syncthreads();
+  const int *__restrict__ cptr = d.cptr;
+  const int *__restrict__ wgt = d.wgt;
+  const double *__restrict__ x2 = d.clv + (long)x2Slot * d.clvStride;
+  const double *__restrict__ x1 =
+      TIP ? nullptr : d.clv + (long)x1Slot * d.clvStride;
+  const unsigned char *__restrict__ tipX1 =
+      TIP ? d.tips + (long)tipSlot * d.tipStride : nullptr;
+  const long n = d.n;
+  const int lane = tid & 63;
+  double acc = 0.0;
+  for (long i = (long)u.b * NV_BLOCK + tid; i < n;
+       i += (long)u.g * NV_BLOCK) {
+    const double *dg = &sD[4 * cptr[i]];
+    const double4 b = *reinterpret_cast<const double4 *>(&x2[i * 4]);
+    double t0, t1;
+    if (TIP) {
+      const double *t = &sTV[4 * tipX1[i]];
+      t0 = t[0] * b.x * dg[0] + t[2] * b.z * dg[2];
+      t1 = t[1] * b.y * dg[1] + t[3] * b.w * dg[3];
+    } else {
+      const double4 a = *reinterpret_cast<const double4 *>(&x1[i * 4]);
+      t0 = a.x * b.x * dg[0] + a.z * b.z * dg[2];
+      t1 = a.y * b.y * dg[1] + a.w * b.w * dg[3];
+    }
+    acc += (double)wgt[i] * log(fabs(t0 + t1));
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
+  if (lane == 0) sRed[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    double s = 0;
+#pragma unroll
+    for (int w = 0; w < NV_BLOCK / 64; w++) s += sRed[w];
+    partials[blockIdx.x] = s;
+  }
+}
+
+/* k_sum_dna_cat over all partitions, into each partition's own sum buffer */
+template <int TC>
+__global__ __launch_bounds__(NV_BLOCK) CATM_NO_PK_F32 void
+k_sum_dna_cat_mseg(const MCatDesc *__restrict__ parts,
+                   const int *__restrict__ unitPart,
+                   const int *__restrict__ unitPrefix,
+                   const double *__restrict__ active,
+                   double *const *__restrict__ sums, int x1Slot, int x2Slot,
+                   int tipSlot, int tipSlot2) {
+  const CatrUnit u = catr_unit(unitPart, unitPrefix);
+  if (active[u.p] == 0.0) return;
+  __shared__ double sTV[64];
+  const MCatDesc d = parts[u.p];
+  const int tid = threadIdx.x;
+  if (TC != EXAML_INNER_INNER && tid < 64) sTV[tid] = d.tipVec[tid];
+  if (TC != EXAML_INNER_INNER) __syncthreads();
+  double *__restrict__ sum = sums[u.p];
+  const double *__restrict__ x1 =
+      TC == EXAML_INNER_INNER ? d.clv + (long)x1Slot * d.clvStride : nullptr;
+  const double *__restrict__ x2 =
+      TC != EXAML_TIP_TIP ? d.clv + (long)x2Slot * d.clvStride : nullptr;
+  const unsigned char *__restrict__ tipX1 =
+      TC != EXAML_INNER_INNER ? d.tips + (long)tipSlot * d.tipStride : nullptr;
+  const unsigned char *__restrict__ tipX2 =
+      TC == EXAML_TIP_TIP ? d.tips + (long)tipSlot2 * d.tipStride : nullptr;
+  const long n = d.n;
+  for (long i = (long)u.b * NV_BLOCK + tid; i < n;
+       i += (long)u.g * NV_BLOCK) {
+    double4 a, b;
+    if (TC == EXAML_TIP_TIP) {
+      const double *t1 = &sTV[4 * tipX1[i]];
+      const double *t2 = &sTV[4 * tipX2[i]];
+      a = make_double4(t1[0], t1[1], t1[2], t1[3]);
+      b = make_double4(t2[0], t2[1], t2[2], t2[3]);
+    } else if (TC == EXAML_TIP_INNER) {
+      const double *t1 = &sTV[4 * tipX1[i]];
+      a = make_double4(t1[0], t1[1], t1[2], t1[3]);
+      b = *reinterpret_cast<const double4 *>(&x2[i * 4]);
+    } else {
+      a = *reinterpret_cast<const double4 *>(&x1[i * 4]);
+      b = *reinterpret_cast<const double4 *>(&x2[i * 4]);
+    }
+    *reinterpret_cast<double4 *>(&sum[i * 4]) =
+        make_double4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w);
+  }
+}
+
+/* k_core_dna_cat over all partitions */
+__global__ __launch_bounds__(NV_BLOCK) CATM_NO_PK_F32 void
+k_core_dna_cat_mseg(const MCatDesc *__restrict__ parts,
+                    const int *__restrict__ unitPart,
+                    const int *__restrict__ unitPrefix,
+                    const double *__restrict__ active,
+                    const double *__restrict__ tabs,
+                    const double *const *__restrict__ sums,
+                    double *__restrict__ partials) {
+  const CatrUnit u = catr_unit(unitPart, unitPrefix);
+  if (active[u.p] == 0.0) return;
+  __shared__ double sD[MAX_CAT * 4], sE1[4], sE2[4], sRp[MAX_CAT],
+      sRed[2][NV_BLOCK / 64];
+  const MCatDesc d = parts[u.p];
+  const double *__restrict__ dtab = tabs + (long)u.p * CATR_TAB;
+  const int numCats = d.numCats;
+  const int tid = threadIdx.x;
+  for (int j = tid; j < numCats * 4; j += NV_BLOCK) sD[j] = dtab[j];
+  if (tid < 4) {
+    sE1[tid] = dtab[numCats * 4 + tid];
+    sE2[tid] = dtab[numCats * 4 + 4 + tid];
+  }
+  for (int j = tid; j < numCats; j += NV_BLOCK)
+    sRp[j] = dtab[numCats * 4 + 8 + j];
+  __syncthreads();
+  const double *__restrict__ sum = sums[u.p];
+  const int *__restrict__ cptr = d.cptr;
+  const int *__restrict__ wgt = d.wgt;
+  const long n = d.n;
+  const int lane = tid & 63;
+  double accD1 = 0.0, accD2 = 0.0;
+  for (long i = (long)u.b * NV_BLOCK + tid; i < n;
+       i += (long)u.g * NV_BLOCK) {
+    const int cat = cptr[i];
+    const double *d1 = &sD[4 * cat];
+    const double r = sRp[cat];
+    const double w = (double)wgt[i];
+    const double wr1 = r * w, wr2 = r * r * w;
+    const double4 s4 = *reinterpret_cast<const double4 *>(&sum[i * 4]);
+    const double te0 = d1[0] * s4.x, to0 = d1[1] * s4.y;
+    const double te1 = d1[2] * s4.z, to1 = d1[3] * s4.w;
+    const double a0 = (te0 + te1) + (to0 + to1);
+    const double a1 = (te0 * sE1[0] + te1 * sE1[2]) +
+                      (to0 * sE1[1] + to1 * sE1[3]);
+    const double a2 = (te0 * sE2[0] + te1 * sE2[2]) +
+                      (to0 * sE2[1] + to1 * sE2[3]);
+    const double inv = 1.0 / fabs(a0);
+    const double dl = a1 * inv, d2l = a2 * inv;
+    accD1 += wr1 * dl;
+    accD2 += wr2 * (d2l - dl * dl);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    accD1 += __shfl_down(accD1, off);
+    accD2 += __shfl_down(accD2, off);
+  }
+  if (lane == 0) {
+    sRed[0][tid >> 6] = accD1;
+    sRed[1][tid >> 6] = accD2;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double s1 = 0, s2 = 0;
+#pragma unroll
+    for (int w = 0; w < NV_BLOCK / 64; w++) {
+      s1 += sRed[0][w];
+      s2 += sRed[1][w];
+    }
+    partials[2 * blockIdx.x] = s1;
+    partials[2 * blockIdx.x + 1] = s2;
+  }
+}
+
+/* k_reduce_lnl per partition: block p folds its g_p partials with the
+ * strided accumulate and the LDS tree of k_reduce_lnl and adds the scaler
+ * undo of that partition.  The output is 0 + s, what k_reduce_lnl leaves in
+ * a cleared cell; a masked partition gets the 0 alone.  (The GAMMA executors
+ * own the names k_reduce_lnl_mseg / k_reduce_2_mseg, hence _cat_.) */
+__global__ __launch_bounds__(NV_BLOCK) void k_reduce_lnl_cat_mseg(
+    const double *__restrict__ partials, const int *__restrict__ unitPrefix,
+    const double *__restrict__ active,
+    unsigned int *const *__restrict__ gsArr, int pNumber, int qNumber,
+    double log_minlik, double *__restrict__ lnl) {
+  const int p = blockIdx.x;
+  const int tid = threadIdx.x;
+  if (active[p] == 0.0) {
+    if (tid == 0) lnl[p] = 0.0;
+    return;
+  }
+  __shared__ double sred[NV_BLOCK];
+  const int u0 = unitPrefix[p], nblocks = unitPrefix[p + 1] - u0;
+  double v = 0;
+  for (int i = tid; i < nblocks; i += NV_BLOCK) v += partials[u0 + i];
+  sred[tid] = v;
+  __syncthreads();
+  for (int off = NV_BLOCK / 2; off > 0; off >>= 1) {
+    if (tid < off) sred[tid] += sred[tid + off];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const unsigned int *gs = gsArr[p];
+    double s = sred[0];
+    s += ((double)gs[pNumber] + (double)gs[qNumber]) * log_minlik;
+    double o = 0.0;
+    o += s;
+    lnl[p] = o;
+  }
+}
+
+/* k_reduce_2 per partition, into out[2p], out[2p + 1] */
+__global__ __launch_bounds__(NV_BLOCK) void k_reduce_2_cat_mseg(
+    const double *__restrict__ partials, const int *__restrict__ unitPrefix,
+    const double *__restrict__ active, double *__restrict__ out) {
+  const int p = blockIdx.x;
+  const int tid = threadIdx.x;
+  if (active[p] == 0.0) {
+    if (tid < 2) out[2 * p + tid] = 0.0;
+    return;
+  }
+  __shared__ double sred[2][NV_BLOCK];
+  const int u0 = unitPrefix[p], nblocks = unitPrefix[p + 1] - u0;
+  double v1 = 0, v2 = 0;
+  for (int i = tid; i < nblocks; i += NV_BLOCK) {
+    v1 += partials[2 * (u0 + i)];
+    v2 += partials[2 * (u0 + i) + 1];
+  }
+  sred[0][tid] = v1;
+  sred[1][tid] = v2;
+  __syncthreads();
+  for (int off = NV_BLOCK / 2; off > 0; off >>= 1) {
+    if (tid < off) {
+      sred[0][tid] += sred[0][tid + off];
+      sred[1][tid] += sred[1][tid + off];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    double o1 = 0.0, o2 = 0.0;
+    o1 += sred[0][0];
+    o2 += sred[1][0];
+    out[2 * p] = o1;
+    out[2 * p + 1] = o2;
+  }
+}
+
+/* ---------------------------------------------------------------------------
  * Host side
  * ------------------------------------------------------------------------ */
 
@@ -339,6 +633,38 @@ extern "C" int examl_hip_multi_cat_plan(int numParts, const long *widths,
   return 0;
 }
 
+/* Unit tables of the root operations, plain host code, no GPU call:
+ * partition p owns g_p = grid_for(widths[p]) units (none for width 0), in
+ * partition order.  prefixOut[numParts + 1] gets the running sum of g_p;
+ * unitPartOut[cap] the partition of every unit (cap < 0: no unit table is
+ * written).  Returns sum(g_p), or -1 before anything is written when it
+ * exceeds a cap >= 0 or INT_MAX, or a width is negative. */
+extern "C" long examl_hip_multi_cat_root_units(int numParts,
+                                               const long *widths,
+                                               int *prefixOut,
+                                               int *unitPartOut, long cap) {
+  if (numParts < 0) return -1;
+  long total = 0;
+  for (int p = 0; p < numParts; p++) {
+    if (widths[p] < 0) return -1;
+    total += widths[p] > 0 ? grid_for(widths[p]) : 0;
+    if (total > 0x7fffffffL) return -1;
+  }
+  if (cap >= 0 && total > cap) return -1;
+  if (cap < 0) unitPartOut = nullptr;
+  long u = 0;
+  for (int p = 0; p < numParts; p++) {
+    prefixOut[p] = (int)u;
+    const int g = widths[p] > 0 ? grid_for(widths[p]) : 0;
+    for (int b = 0; unitPartOut && b < g; b++) unitPartOut[u + b] = p;
+    u += g;
+  }
+  prefixOut[numParts] = (int)u;
+  return total;
+}
+
+extern "C" int examl_hip_multi_cat_root_grid_cap(void) { return MAX_GRID; }
+
 struct examl_hip_multi_cat {
   int numParts = 0, maxOps = 0;
   std::vector<long> widths, clvStride, tipStride;
@@ -360,6 +686,17 @@ struct examl_hip_multi_cat {
   long actOff = 0, pOff = 0, callDoubles = 0;
   int lastFused = 0;
   double lastHostPms = 0; /* host time of the last call's make_p loop */
+  /* root operations: unit tables (built once), block partials (2 per unit)
+   * and the per-call block, one upload:
+   * [MCatDesc x numParts | active x numParts | sum pointers x numParts |
+   *  tables CATR_TAB x numParts], in doubles */
+  std::vector<int> unitPrefix;
+  int numUnits = 0;
+  int *d_unitPrefix = nullptr, *d_unitPart = nullptr;
+  double *d_rootPartials = nullptr;
+  double *d_root = nullptr;
+  long rSumOff = 0, rTabOff = 0, rootDoubles = 0;
+  int lastRoot = 0;
 };
 
 extern "C" void examl_hip_multi_cat_destroy(void *vh) {
@@ -371,6 +708,10 @@ extern "C" void examl_hip_multi_cat_destroy(void *vh) {
   hipFree(h->d_gsArr);
   hipFree(h->d_inc);
   hipFree(h->d_call);
+  hipFree(h->d_unitPrefix);
+  hipFree(h->d_unitPart);
+  hipFree(h->d_rootPartials);
+  hipFree(h->d_root);
   delete h;
 }
 
@@ -462,6 +803,37 @@ extern "C" int examl_hip_multi_cat_create(
                    hipMemcpyHostToDevice));
     MCHK(hipMemcpy(h->d_tileSite0, tsite.data(),
                    (size_t)tiles * sizeof(long), hipMemcpyHostToDevice));
+  }
+  /* root operations */
+  h->unitPrefix.assign((size_t)numParts + 1, 0);
+  const long units = examl_hip_multi_cat_root_units(
+      numParts, widths, h->unitPrefix.data(), nullptr, -1);
+  if (units < 0) {
+    examl_hip_multi_cat_destroy(h);
+    snprintf(g_err, sizeof(g_err), "multi_cat_create: unit table");
+    return -1;
+  }
+  h->numUnits = (int)units;
+  h->rSumOff = h->pOff; /* descriptors | active, as in d_call */
+  h->rTabOff = h->rSumOff + numParts;
+  h->rootDoubles = h->rTabOff + (long)numParts * CATR_TAB;
+  MCHK(hipMalloc(&h->d_root, (size_t)h->rootDoubles * sizeof(double)));
+  MCHK(hipMalloc(&h->d_unitPrefix, ((size_t)numParts + 1) * sizeof(int)));
+  MCHK(hipMemcpy(h->d_unitPrefix, h->unitPrefix.data(),
+                 ((size_t)numParts + 1) * sizeof(int),
+                 hipMemcpyHostToDevice));
+  if (units > 0) {
+    std::vector<int> upart((size_t)units);
+    if (examl_hip_multi_cat_root_units(numParts, widths, h->unitPrefix.data(),
+                                       upart.data(), units) != units) {
+      examl_hip_multi_cat_destroy(h);
+      snprintf(g_err, sizeof(g_err), "multi_cat_create: unit table");
+      return -1;
+    }
+    MCHK(hipMalloc(&h->d_unitPart, (size_t)units * sizeof(int)));
+    MCHK(hipMemcpy(h->d_unitPart, upart.data(), (size_t)units * sizeof(int),
+                   hipMemcpyHostToDevice));
+    MCHK(hipMalloc(&h->d_rootPartials, (size_t)units * 2 * sizeof(double)));
   }
 #undef MCHK
   *out = h;
@@ -654,4 +1026,268 @@ extern "C" int examl_hip_newview_traversal_multi_cat(
     }
     return 0;
   });
+}
+
+/* ---------------------------------------------------------------------------
+ * Root operations: host executors
+ * ------------------------------------------------------------------------ */
+
+extern "C" int examl_hip_multi_cat_root_kernels(void *vh) {
+  return vh ? ((examl_hip_multi_cat *)vh)->lastRoot : 0;
+}
+
+/* Checks a call's categories and fills the descriptors and active flags of
+ * the pinned stage of d_root; hostP_get waits for the stage's previous copy
+ * first.  live[p] = the partition has sites and is not masked. */
+static HostPSlot *catr_stage(examl_hip_multi_cat *h, const char *who,
+                             const int *numCats, const int *const *dev_cptrs,
+                             const unsigned char *activeMask,
+                             std::vector<unsigned char> &live) {
+  const int NP = h->numParts;
+  std::vector<int> catOff((size_t)NP);
+  long pRow = 0;
+  if (examl_hip_multi_cat_plan(NP, h->widths.data(), numCats, MAX_CAT,
+                               catOff.data(), &pRow) != 0) {
+    snprintf(g_err, sizeof(g_err), "%s: numCats outside 1..%d", who, MAX_CAT);
+    return nullptr;
+  }
+  HostPSlot *slot = hostP_get(h->d_root, (size_t)h->rootDoubles);
+  MCatDesc *desc = reinterpret_cast<MCatDesc *>(slot->buf);
+  live.assign((size_t)NP, 0);
+  for (int p = 0; p < NP; p++) {
+    live[(size_t)p] = h->widths[p] > 0 && (!activeMask || activeMask[p]);
+    desc[p] = {h->clv[p], h->tips[p], h->wgt[p], dev_cptrs[p], h->EV[p],
+               h->tipVec[p], (int)h->clvStride[p], (int)h->tipStride[p],
+               (int)h->widths[p], h->widths[p] > 0 ? numCats[p] : 0,
+               catOff[(size_t)p]};
+    slot->buf[h->actOff + p] = live[(size_t)p] ? 1.0 : 0.0;
+  }
+  return slot;
+}
+
+/* the ONE copy of a call: the first `doubles` of the stage */
+static int catr_upload(examl_hip_multi_cat *h, HostPSlot *slot, long doubles,
+                       hipStream_t s) {
+  hipError_t err =
+      hipMemcpyAsync(h->d_root, slot->buf, (size_t)doubles * sizeof(double),
+                     hipMemcpyHostToDevice, s);
+  if (err != hipSuccess) return set_err(err, "multi_cat root upload");
+  (void)hipEventRecord(slot->ev, s);
+  slot->ev_valid = true;
+  return 0;
+}
+
+/* a live partition without a sum buffer is refused before anything runs */
+static bool catr_null_sum(const examl_hip_multi_cat *h, const char *who,
+                          double *const *dev_sums,
+                          const std::vector<unsigned char> &live) {
+  for (int p = 0; p < h->numParts; p++)
+    if (live[(size_t)p] && !dev_sums[p]) {
+      snprintf(g_err, sizeof(g_err), "%s: partition %d has no sum buffer",
+               who, p);
+      return true;
+    }
+  return false;
+}
+
+static bool catr_fused(const examl_hip_multi_cat *h) {
+  return h->numUnits > 0 && g_multi_fused && g_use_fused;
+}
+
+/* the loop path accumulates into its outputs like the engines' kernels */
+static int catr_clear(double *dev, int doubles, hipStream_t s) {
+  hipLaunchKernelGGL(k_clear_u32, dim3((unsigned)((2 * doubles + 255) / 256)),
+                     dim3(256), 0, s, (unsigned int *)dev, 2L * doubles);
+  hipError_t err = hipGetLastError();
+  return err == hipSuccess ? 0 : set_err(err, "multi_cat root clear");
+}
+
+extern "C" int examl_hip_evaluate_root_multi_cat(
+    void *vh, int rootTipCase, int pNumber, int qNumber, int x1Slot,
+    int x2Slot, int tipSlot, const double *zs, const double *const *EIGNs,
+    const double *const *perSiteRates, const int *numCats,
+    const int *const *dev_cptrs, const unsigned char *activeMask,
+    double *dev_lnl, void *stream) {
+  examl_hip_multi_cat *h = (examl_hip_multi_cat *)vh;
+  if (!h) {
+    snprintf(g_err, sizeof(g_err), "evaluate_root_multi_cat: null handle");
+    return -1;
+  }
+  h->lastRoot = 0;
+  if (rootTipCase != EXAML_TIP_INNER && rootTipCase != EXAML_INNER_INNER) {
+    snprintf(g_err, sizeof(g_err), "evaluate_root_multi_cat: bad tipCase %d",
+             rootTipCase);
+    return -1;
+  }
+  const int NP = h->numParts;
+  std::vector<unsigned char> live;
+  HostPSlot *slot = catr_stage(h, "evaluate_root_multi_cat", numCats,
+                               dev_cptrs, activeMask, live);
+  if (!slot) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  (void)hipGetLastError();
+  double *d_tabs = h->d_root + h->rTabOff;
+
+  if (!catr_fused(h)) {
+    /* evaluateIterative's partition loop over the per-engine launches */
+    if (catr_clear(dev_lnl, NP, s) != 0) return -1;
+    for (int p = 0; p < NP; p++) {
+      if (!live[(size_t)p]) continue;
+      if (examl_hip_evaluate_root_dna_cat_x(
+              rootTipCase, pNumber, qNumber, x1Slot, x2Slot, tipSlot, zs[p],
+              EIGNs[p], perSiteRates[p], numCats[p], h->tipVec[p],
+              dev_cptrs[p], h->clv[p], h->clvStride[p], h->tips[p],
+              h->tipStride[p], h->wgt[p], h->widths[p], h->scalers[p],
+              d_tabs + (long)p * CATR_TAB,
+              h->d_rootPartials + h->unitPrefix[(size_t)p], dev_lnl + p,
+              stream) != 0)
+        return -1;
+    }
+    return 0;
+  }
+
+  for (int p = 0; p < NP; p++)
+    if (live[(size_t)p])
+      examl_host_calc_diagptable(
+          zs[p], 4, numCats[p], perSiteRates[p], EIGNs[p],
+          slot->buf + h->rTabOff + (long)p * CATR_TAB);
+  if (catr_upload(h, slot, h->rootDoubles, s) != 0) return -1;
+  const MCatDesc *d_parts = reinterpret_cast<const MCatDesc *>(h->d_root);
+  const double *d_active = h->d_root + h->actOff;
+  with_flag(rootTipCase == EXAML_TIP_INNER, [&](auto tip) {
+    hipLaunchKernelGGL((k_evaluate_dna_cat_mseg<decltype(tip)::value>),
+                       dim3(h->numUnits), dim3(NV_BLOCK), 0, s, d_parts,
+                       h->d_unitPart, h->d_unitPrefix, d_active, d_tabs,
+                       x1Slot, x2Slot, tipSlot, h->d_rootPartials);
+  });
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return set_err(err, "multi_cat evaluate launch");
+  hipLaunchKernelGGL(k_reduce_lnl_cat_mseg, dim3(NP), dim3(NV_BLOCK), 0, s,
+                     h->d_rootPartials, h->d_unitPrefix, d_active, h->d_gsArr,
+                     pNumber, qNumber, log(MINLIKELIHOOD), dev_lnl);
+  err = hipGetLastError();
+  if (err != hipSuccess) return set_err(err, "multi_cat evaluate reduce");
+  h->lastRoot = 1;
+  return 0;
+}
+
+extern "C" int examl_hip_sum_root_multi_cat(
+    void *vh, int rootTipCase, int x1Slot, int x2Slot, int tipSlot,
+    int tipSlot2, const int *numCats, const int *const *dev_cptrs,
+    double *const *dev_sums, const unsigned char *activeMask, void *stream) {
+  examl_hip_multi_cat *h = (examl_hip_multi_cat *)vh;
+  if (!h) {
+    snprintf(g_err, sizeof(g_err), "sum_root_multi_cat: null handle");
+    return -1;
+  }
+  h->lastRoot = 0;
+  if (rootTipCase < EXAML_TIP_TIP || rootTipCase > EXAML_INNER_INNER) {
+    snprintf(g_err, sizeof(g_err), "sum_root_multi_cat: bad tipCase %d",
+             rootTipCase);
+    return -1;
+  }
+  const int NP = h->numParts;
+  std::vector<unsigned char> live;
+  HostPSlot *slot = catr_stage(h, "sum_root_multi_cat", numCats, dev_cptrs,
+                               activeMask, live);
+  if (!slot) return -1;
+  if (catr_null_sum(h, "sum_root_multi_cat", dev_sums, live)) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  (void)hipGetLastError();
+
+  if (!catr_fused(h)) {
+    for (int p = 0; p < NP; p++) {
+      if (!live[(size_t)p]) continue;
+      if (examl_hip_sum_root_dna_cat(rootTipCase, x1Slot, x2Slot, tipSlot,
+                                     tipSlot2, h->tipVec[p], h->clv[p],
+                                     h->clvStride[p], h->tips[p],
+                                     h->tipStride[p], dev_sums[p],
+                                     h->widths[p], stream) != 0)
+        return -1;
+    }
+    return 0;
+  }
+
+  memcpy(slot->buf + h->rSumOff, dev_sums, (size_t)NP * sizeof(double *));
+  if (catr_upload(h, slot, h->rTabOff, s) != 0) return -1;
+  const MCatDesc *d_parts = reinterpret_cast<const MCatDesc *>(h->d_root);
+  const double *d_active = h->d_root + h->actOff;
+  double *const *d_sums =
+      reinterpret_cast<double *const *>(h->d_root + h->rSumOff);
+#define CATR_SUM(TC)                                                         \
+  hipLaunchKernelGGL((k_sum_dna_cat_mseg<TC>), dim3(h->numUnits),            \
+                     dim3(NV_BLOCK), 0, s, d_parts, h->d_unitPart,           \
+                     h->d_unitPrefix, d_active, d_sums, x1Slot, x2Slot,      \
+                     tipSlot, tipSlot2)
+  switch (rootTipCase) {
+  case EXAML_TIP_TIP: CATR_SUM(EXAML_TIP_TIP); break;
+  case EXAML_TIP_INNER: CATR_SUM(EXAML_TIP_INNER); break;
+  default: CATR_SUM(EXAML_INNER_INNER);
+  }
+#undef CATR_SUM
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return set_err(err, "multi_cat sum launch");
+  h->lastRoot = 1;
+  return 0;
+}
+
+extern "C" int examl_hip_core_root_multi_cat(
+    void *vh, const double *lzs, const double *const *EIGNs,
+    const double *const *perSiteRates, const int *numCats,
+    const int *const *dev_cptrs, double *const *dev_sums,
+    const unsigned char *activeMask, double *dev_out2, void *stream) {
+  examl_hip_multi_cat *h = (examl_hip_multi_cat *)vh;
+  if (!h) {
+    snprintf(g_err, sizeof(g_err), "core_root_multi_cat: null handle");
+    return -1;
+  }
+  h->lastRoot = 0;
+  const int NP = h->numParts;
+  std::vector<unsigned char> live;
+  HostPSlot *slot = catr_stage(h, "core_root_multi_cat", numCats, dev_cptrs,
+                               activeMask, live);
+  if (!slot) return -1;
+  if (catr_null_sum(h, "core_root_multi_cat", dev_sums, live)) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  (void)hipGetLastError();
+  double *d_tabs = h->d_root + h->rTabOff;
+
+  if (!catr_fused(h)) {
+    /* execCore's partition loop over the per-engine launches */
+    if (catr_clear(dev_out2, 2 * NP, s) != 0) return -1;
+    for (int p = 0; p < NP; p++) {
+      if (!live[(size_t)p]) continue;
+      if (examl_hip_core_root_dna_cat(
+              h->widths[p], dev_sums[p], EIGNs[p], perSiteRates[p],
+              numCats[p], lzs[p], h->wgt[p], dev_cptrs[p],
+              d_tabs + (long)p * CATR_TAB,
+              h->d_rootPartials + 2L * h->unitPrefix[(size_t)p],
+              dev_out2 + 2 * p, stream) != 0)
+        return -1;
+    }
+    return 0;
+  }
+
+  for (int p = 0; p < NP; p++)
+    if (live[(size_t)p])
+      examl_host_core_dtables_dna_cat(
+          EIGNs[p], perSiteRates[p], numCats[p], lzs[p],
+          slot->buf + h->rTabOff + (long)p * CATR_TAB);
+  memcpy(slot->buf + h->rSumOff, dev_sums, (size_t)NP * sizeof(double *));
+  if (catr_upload(h, slot, h->rootDoubles, s) != 0) return -1;
+  const MCatDesc *d_parts = reinterpret_cast<const MCatDesc *>(h->d_root);
+  const double *d_active = h->d_root + h->actOff;
+  const double *const *d_sums =
+      reinterpret_cast<const double *const *>(h->d_root + h->rSumOff);
+  hipLaunchKernelGGL(k_core_dna_cat_mseg, dim3(h->numUnits), dim3(NV_BLOCK),
+                     0, s, d_parts, h->d_unitPart, h->d_unitPrefix, d_active,
+                     d_tabs, d_sums, h->d_rootPartials);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return set_err(err, "multi_cat core launch");
+  hipLaunchKernelGGL(k_reduce_2_cat_mseg, dim3(NP), dim3(NV_BLOCK), 0, s,
+                     h->d_rootPartials, h->d_unitPrefix, d_active, dev_out2);
+  err = hipGetLastError();
+  if (err != hipSuccess) return set_err(err, "multi_cat core reduce");
+  h->lastRoot = 1;
+  return 0;
 }

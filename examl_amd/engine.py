@@ -951,8 +951,13 @@ class MultiDnaCatEngine:
     (newviewGenericSpecial.c:939).  Wraps per-partition DnaCatEngine
     buffers; P blocks come from the host like the engines' own, so CLVs,
     scaler counts and lnL are bit-identical to running each engine's
-    newview_traversal.  Evaluate, sum and core stay with the engines, which
-    read the same CLV pools."""
+    newview_traversal.  evaluate_root, sum_root and core_derivs_vec run the
+    root operations the same way (evaluateIterative / makenewzIterative /
+    execCore partition loops): one kernel over all partitions plus one
+    reduction block per partition, every block doing what a block of the
+    engine's own launch does, so per-partition lnL, sum buffers and
+    derivatives are bit-identical to DnaCatEngine.evaluate_root, sum_root
+    and core_derivs_async."""
 
     def __init__(self, engines):
         assert engines and all(type(e) is DnaCatEngine for e in engines)
@@ -980,6 +985,9 @@ class MultiDnaCatEngine:
             parr([e.d_tipVector.data_ptr() for e in engines]),
             self.max_ops, ctypes.byref(h)), "multi_cat_create")
         self.h = h
+        self.d_lnl = torch.zeros(NP, dtype=torch.float64, device=self.device)
+        self.d_out2 = torch.zeros((NP, 2), dtype=torch.float64,
+                                  device=self.device)
 
     def __del__(self):
         try:
@@ -1031,6 +1039,98 @@ class MultiDnaCatEngine:
         """On-chip kernel launches of the last newview_traversal call (0
         when it ran the per-partition loop)."""
         return lib().examl_hip_multi_cat_fused_launches(self.h)
+
+    # root operations: the engines' category tensors, numCats, rates and
+    # models are read at every call, like newview_traversal does
+
+    def _stream(self):
+        return ctypes.c_void_p(
+            torch.cuda.current_stream().cuda_stream
+            if self.device.type == "cuda" else 0)
+
+    def _hostp(self, arrays):
+        return (ctypes.c_void_p * self.NP)(*[a.ctypes.data for a in arrays])
+
+    def _cats(self):
+        engs = self.engines
+        return ((ctypes.c_int * self.NP)(*[e.num_cats for e in engs]),
+                (ctypes.c_void_p * self.NP)(
+                    *[e.d_cptr.data_ptr() for e in engs]))
+
+    def _mask(self, active):
+        if active is None:
+            return None
+        return (ctypes.c_ubyte * self.NP)(*[1 if a else 0 for a in active])
+
+    def _per_part(self, v):
+        """scalar (joint branch) or per-partition sequence (-M) -> [NP]"""
+        a = np.atleast_1d(np.asarray(v, dtype=np.float64))
+        a = np.repeat(a, self.NP) if a.size == 1 else a
+        assert a.size == self.NP
+        return np.ascontiguousarray(a)
+
+    def _sums(self):
+        return (ctypes.c_void_p * self.NP)(
+            *[e.d_sum.data_ptr() if e.d_sum is not None else 0
+              for e in self.engines])
+
+    def evaluate_root(self, tree, p, q, z, active=None):
+        """z: scalar (joint) or per-partition sequence (-M).  Returns the
+        per-partition lnL device vector [NP]; masked and empty partitions
+        hold 0."""
+        engs = self.engines
+        tc, x1s, x2s, tslot, _, pn, qn = engs[0]._root_case(tree, p, q)
+        num_cats, cptrs = self._cats()
+        zv = self._per_part(z)
+        check(lib().examl_hip_evaluate_root_multi_cat(
+            self.h, tc, pn, qn, x1s, x2s, tslot, _np_vp(zv),
+            self._hostp([e.model.EIGN for e in engs]),
+            self._hostp([e.per_site_rates for e in engs]), num_cats, cptrs,
+            self._mask(active), _vp(self.d_lnl), self._stream()),
+            "evaluate_root_multi_cat")
+        return self.d_lnl
+
+    def sum_root(self, tree, p, q, active=None):
+        """The engines' sum buffers (allocated here where an engine has
+        none yet) get what each engine's own sum_root writes."""
+        for m, e in enumerate(self.engines):
+            if e.d_sum is None and e.width > 0 and \
+                    (active is None or active[m]):
+                e.d_sum = torch.empty(e.width * 4, dtype=torch.float64,
+                                      device=e.device)
+        p_tip, q_tip = tree.is_tip(p), tree.is_tip(q)
+        if p_tip and q_tip:
+            tc, x1s, x2s, t1, t2 = TIP_TIP, -1, -1, p, q
+        elif q_tip:
+            tc, x1s, x2s, t1, t2 = TIP_INNER, -1, tree.clv_slot(p), q, -1
+        elif p_tip:
+            tc, x1s, x2s, t1, t2 = TIP_INNER, -1, tree.clv_slot(q), p, -1
+        else:
+            tc, x1s, x2s, t1, t2 = (INNER_INNER, tree.clv_slot(p),
+                                    tree.clv_slot(q), -1, -1)
+        num_cats, cptrs = self._cats()
+        check(lib().examl_hip_sum_root_multi_cat(
+            self.h, tc, x1s, x2s, t1, t2, num_cats, cptrs, self._sums(),
+            self._mask(active), self._stream()), "sum_root_multi_cat")
+
+    def core_derivs_vec(self, lz, active=None):
+        """Per-partition {dlnL, d2lnL}, device tensor [NP, 2]; lz scalar or
+        per-partition.  Needs sum_root first."""
+        engs = self.engines
+        num_cats, cptrs = self._cats()
+        lzv = self._per_part(lz)
+        check(lib().examl_hip_core_root_multi_cat(
+            self.h, _np_vp(lzv),
+            self._hostp([e.model.EIGN for e in engs]),
+            self._hostp([e.per_site_rates for e in engs]), num_cats, cptrs,
+            self._sums(), self._mask(active), _vp(self.d_out2),
+            self._stream()), "core_root_multi_cat")
+        return self.d_out2
+
+    def root_kernels(self):
+        """All-partition kernels of the last evaluate_root / sum_root /
+        core_derivs_vec call (0 when it ran the per-partition loop)."""
+        return lib().examl_hip_multi_cat_root_kernels(self.h)
 
 
 class SaveProtEngine(SaveDnaEngine):

@@ -100,9 +100,9 @@ class TreeSearch:
                 self.fused = MultiEngine(engines)
             except Exception:
                 self.fused = None
-        # partitioned DNA PSR: the traversal alone goes through one on-chip
-        # kernel over all partitions (MultiDnaCatEngine); evaluate, sum and
-        # core stay with the engines, which read the same CLV pools
+        # partitioned DNA PSR: the traversal and the root operations
+        # (evaluate, sum, core) each go through one kernel over all
+        # partitions (MultiDnaCatEngine), bit-identical to the engines' own
         self.fused_cat = None
         if (self.M > 1 and rate_het == "CAT"
                 and all(type(e).__name__ == "DnaCatEngine" for e in engines)
@@ -309,6 +309,17 @@ class TreeSearch:
                     self.per_partition_lnl[m] = float(vec[m])
             self.likelihood = sum(self.per_partition_lnl)
             return self.likelihood
+        if self.fused_cat is not None:
+            # the loop branch below with ONE launch: same bits per
+            # partition, same float() conversions, same host sum
+            vals = self.fused_cat.evaluate_root(
+                t, p, q, zv[:self.NB] if self.NB > 1 else z,
+                active=self.execute_model).cpu()
+            for m in range(self.M):
+                if self.execute_model[m]:
+                    self.per_partition_lnl[m] = float(vals[m])
+            self.likelihood = sum(self.per_partition_lnl)
+            return self.likelihood
         outs = []
         for m, eng in enumerate(self.engines):
             if self.execute_model[m]:
@@ -339,6 +350,10 @@ class TreeSearch:
         if self.fused is not None:
             self.fused.sum_root(self.tree, p, q,
                                 active=self.execute_model)
+        elif self.fused_cat is not None:
+            self.fused_cat.sum_root(self.tree, p, q,
+                                    active=self.execute_model)
+            live = [m for m in range(self.M) if self.execute_model[m]]
         else:
             for m, eng in enumerate(self.engines):
                 if self.execute_model[m]:
@@ -363,6 +378,14 @@ class TreeSearch:
                     lz, active=self.execute_model).cpu().numpy()
                 dlnL = float(v[0::2].sum())
                 d2lnL = float(v[1::2].sum())
+            elif self.fused_cat is not None:
+                # the [k, 2] tensor torch.stack gives the loop branch below
+                # (active partitions in order), reduced by the same calls
+                vals = self.fused_cat.core_derivs_vec(
+                    lz, active=self.execute_model).cpu()[live]
+                if live:
+                    dlnL = float(vals[:, 0].sum())
+                    d2lnL = float(vals[:, 1].sum())
             else:
                 outs = [eng.core_derivs_async(lz)
                         for m, eng in enumerate(self.engines)
@@ -445,6 +468,9 @@ class TreeSearch:
                 if self.fused is not None:
                     self.fused.sum_root(self.tree, p, q,
                                         active=self.execute_model)
+                elif self.fused_cat is not None:
+                    self.fused_cat.sum_root(self.tree, p, q,
+                                            active=self.execute_model)
                 else:
                     for m, eng in enumerate(self.engines):
                         if self.execute_model[m]:
@@ -458,6 +484,12 @@ class TreeSearch:
                 for m in range(NB):
                     if self.execute_model[m]:
                         dl[m], d2[m] = v[2 * m], v[2 * m + 1]
+            elif self.fused_cat is not None:
+                vals = self.fused_cat.core_derivs_vec(
+                    corelz, active=self.execute_model).cpu()
+                for m in range(NB):
+                    if self.execute_model[m]:
+                        dl[m], d2[m] = float(vals[m][0]), float(vals[m][1])
             else:
                 outs = [(m, eng.core_derivs_async(float(corelz[m])))
                         for m, eng in enumerate(self.engines)

@@ -833,6 +833,64 @@ int examl_hip_multi_cat_plan(int numParts, const long *widths,
                              const int *numCats, int maxCat, int *catOff,
                              long *pRow);
 
+/* ---------------------------------------------------------------------------
+ * Root operations of partitioned DNA PSR over all partitions: the partition
+ * loops of evaluateIterative (evaluateGenericSpecial.c:403), makenewzIterative
+ * and execCore (makenewzGenericSpecial.c:885) around the GTRCAT cases as ONE
+ * kernel per call plus one reduction block per partition, on the handle of
+ * examl_hip_multi_cat_create.
+ *
+ * Unit of work = (partition, virtual block): partition p of n_p sites owns
+ * g_p = min(ceil(n_p / 256), grid cap) consecutive units, the grid its own
+ * engine launches, and unit (p, b) runs the per-engine kernel's loop, so
+ * per-partition lnL, sum buffers and both derivatives are bit-identical to
+ * examl_hip_evaluate_root_dna_cat_x, examl_hip_sum_root_dna_cat and
+ * examl_hip_core_root_dna_cat.
+ *
+ * Per call: EIGN, rates, numCats and dev_cptr per partition (as the
+ * traversal entry; optimizeRateCategories replaces them), zs / lzs
+ * [numParts] (one branch length: repeated), dev_sums[numParts] the
+ * partitions' sum buffers (4 * width doubles; null allowed where the
+ * partition is empty or masked), activeMask the executeModel gating.  The
+ * diag / derivative tables are made on the host (examl_host_calc_diagptable,
+ * examl_host_core_dtables_dna_cat) into a pinned stage that goes up with the
+ * descriptors in one copy; a later call waits for that copy before it
+ * refills the stage.  dev_lnl[numParts] / dev_out2[2 * numParts] are
+ * written, not accumulated: a masked or empty partition gets 0, its sum
+ * buffer is untouched and none of its buffers is dereferenced.
+ * numCats outside 1..25 on a partition with sites or an unknown tip case is
+ * refused before anything runs.  examl_hip_use_fused(0) /
+ * examl_hip_multi_use_fused(0) make the same entry points loop over the
+ * per-partition launches.
+ * examl_hip_multi_cat_root_kernels: all-partition kernels (reductions not
+ * counted) of the last root call on h; 0 when the loop ran.
+ * examl_hip_multi_cat_root_units: the unit tables, plain host code:
+ * prefixOut[numParts + 1] = running sum of g_p, unitPartOut[cap] = partition
+ * of every unit (cap < 0: no unit table); returns sum(g_p), or -1 before
+ * anything is written when that exceeds a cap >= 0 or INT_MAX or a width is
+ * negative.  examl_hip_multi_cat_root_grid_cap: the grid cap.
+ * ------------------------------------------------------------------------ */
+int examl_hip_evaluate_root_multi_cat(
+    void *h, int rootTipCase, int pNumber, int qNumber, int x1Slot,
+    int x2Slot, int tipSlot, const double *zs, const double *const *EIGNs,
+    const double *const *perSiteRates, const int *numCats,
+    const int *const *dev_cptrs, const unsigned char *activeMask,
+    double *dev_lnl, void *stream);
+int examl_hip_sum_root_multi_cat(
+    void *h, int rootTipCase, int x1Slot, int x2Slot, int tipSlot,
+    int tipSlot2, const int *numCats, const int *const *dev_cptrs,
+    double *const *dev_sums, const unsigned char *activeMask, void *stream);
+int examl_hip_core_root_multi_cat(
+    void *h, const double *lzs, const double *const *EIGNs,
+    const double *const *perSiteRates, const int *numCats,
+    const int *const *dev_cptrs, double *const *dev_sums,
+    const unsigned char *activeMask, double *dev_out2, void *stream);
+int examl_hip_multi_cat_root_kernels(void *h);
+long examl_hip_multi_cat_root_units(int numParts, const long *widths,
+                                    int *prefixOut, int *unitPartOut,
+                                    long cap);
+int examl_hip_multi_cat_root_grid_cap(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,7 @@ categories, the bench tree.  One step is DnaCatEngine.full_lnl: a full
 traversal (48 newview entries) plus the root evaluation.
 
   python tools/cat_step_time.py --steps K --warmup W --fused 0|1
-                                [--partitions N] [--entries E]
+                                [--partitions N] [--entries E] [--makenewz K]
 
 --fused sets examl_hip_use_fused; on a build without the on-chip CAT kernel
 it changes nothing on this path.  Inputs are seeded and generated here.
@@ -13,7 +13,12 @@ set each; a step is then one traversal of all partitions (through
 MultiDnaCatEngine where the build has it, else the loop over the engines)
 plus the root evaluation of every partition and ONE synchronise.  --entries
 E times a partial traversal instead: the last E entries of the list, after
-one full traversal.  With partitions, host_p_ms is the executor's own host
+one full traversal.  --makenewz K (with partitions) times a branch-length
+step instead: sum_root of all partitions plus K core evaluations, each read
+back to the host as the Newton-Raphson loop of TreeSearch.makenewz_generic
+does.  Evaluate, sum and core go through MultiDnaCatEngine where the build
+has them there (root_ops in the output), else through the loop over the
+engines.  With partitions, host_p_ms is the executor's own host
 timer around the make_p loop of the last step
 (examl_hip_multi_cat_host_p_ms; null on a build without it) and upload_ms
 the time of one pinned copy of one step's P bytes, made and synchronised
@@ -90,9 +95,34 @@ def partitioned(args):
             for e in engs:
                 e.newview_traversal(lst)
 
-    def step():
-        traverse(timed)
+    root_ops = hasattr(multi, "core_derivs_vec")
+    lzs = np.log(np.linspace(0.2, 0.9, max(args.makenewz, 1)))
+
+    def evaluate():
+        if root_ops:
+            return [multi.evaluate_root(tree, p, q, z)]
         return [e.evaluate_root(tree, p, q, z) for e in engs]
+
+    def makenewz():
+        if root_ops:
+            multi.sum_root(tree, p, q)
+        else:
+            for e in engs:
+                e.sum_root(tree, p, q)
+        for lz in lzs:
+            if root_ops:
+                vals = multi.core_derivs_vec(float(lz)).cpu()
+            else:
+                vals = torch.stack([e.core_derivs_async(float(lz))
+                                    for e in engs]).cpu()
+            d1, d2 = float(vals[:, 0].sum()), float(vals[:, 1].sum())
+        return d1, d2
+
+    def step():
+        if args.makenewz:
+            return makenewz()
+        traverse(timed)
+        return evaluate()
 
     L.examl_hip_use_fused(args.fused)
     try:
@@ -126,7 +156,11 @@ def partitioned(args):
         "entries": len(timed),
         "host_p_ms": make_ms,
         "upload_ms": up_ms,
-        "lnl": repr(float(sum(o.item() for o in outs))),
+        "root_ops": root_ops,
+        "makenewz": args.makenewz,
+        "lnl": repr(float(sum(float(v) for o in evaluate()
+                              for v in o.cpu().reshape(-1)))),
+        "derivs": [repr(x) for x in outs] if args.makenewz else None,
     }), flush=True)
 
 
@@ -140,6 +174,7 @@ def main():
     ap.add_argument("--cats", type=int, default=25)
     ap.add_argument("--partitions", type=int, default=1)
     ap.add_argument("--entries", type=int, default=0)
+    ap.add_argument("--makenewz", type=int, default=0)
     args = ap.parse_args()
     if args.partitions > 1:
         return partitioned(args)
