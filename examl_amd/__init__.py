@@ -168,6 +168,19 @@ def _bind(lib):
     lib.examl_host_evaluate_partial_dna_cat.restype = ctypes.c_double
     lib.examl_host_evaluate_partial_dna_cat.argtypes = \
         [p, i, i, i, d, l, d, i, p, p, p, p, p, l, i]
+    # per-site rate search of optimizeRateCategories on the GPU
+    lib.examl_host_rate_scan_plan.argtypes = [p, i, i, p, p]
+    lib.examl_hip_rate_scan_dna_cat.argtypes = \
+        [p, i, i, i, i, d, p, p, p, p, p, l, p, l, d, d, i, i, p, p, p, l,
+         p, l, p]
+    lib.examl_hip_rate_scan_table_bytes.argtypes = [i]
+    lib.examl_hip_rate_scan_table_bytes.restype = l
+    lib.examl_hip_rate_scan_scratch_bytes.argtypes = [i, l, i]
+    lib.examl_hip_rate_scan_scratch_bytes.restype = l
+    lib.examl_hip_rate_scan_lanes.argtypes = []
+    lib.examl_hip_use_rate_kernel.argtypes = [i]
+    lib.examl_hip_rate_kernel_launches.argtypes = []
+    lib.examl_hip_rate_scan_slot_home.argtypes = []
     lib.examl_hip_use_graphs.argtypes = [i]
     lib.examl_hip_graphs_clear.argtypes = []
     lib.examl_hip_use_fused.argtypes = [i]

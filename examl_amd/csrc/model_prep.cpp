@@ -14,6 +14,7 @@
 
 #include <assert.h>
 #include <math.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "../../include/examl_hip.h"
@@ -710,4 +711,79 @@ extern "C" void examl_host_core_dtables_prot_cat(const double *EIGN,
     for (int l = 1; l < 20; l++) d[20 * i + l] = exp(dd[l] * rptr[i]);
     rw[i] = rptr[i];
   }
+}
+
+/* ---------------------------------------------------------------------------
+ * Slot planner of the per-site rate-scan kernel (k_rate_scan_dna_cat,
+ * examl_dna_cat_rates.inc).  evaluatePartialGeneric keeps one lVector entry
+ * per inner node (evaluatePartialGenericSpecial.c:259); the kernel keeps
+ * only the results that are still waiting for their consumer.  One liveness
+ * pass over the post-order list: an entry's inner operands give their slots
+ * back (the kernel has both in registers before it writes x3), then the
+ * result takes the lowest free slot.  A slot count therefore grows only
+ * while every slot is live, so *L_out is the largest number of results
+ * live at once.  A result nobody consumes (the root's q) stays live to the
+ * end.  Returns 0, or -1 for a list that is no post-order walk: an inner
+ * operand no earlier entry produced or that was consumed already, a node
+ * produced twice while live, ids out of range.
+ * ------------------------------------------------------------------------ */
+extern "C" int examl_host_rate_scan_plan(const void *ops_, int numOps,
+                                         int mxtips, int *slot_out,
+                                         int *L_out) {
+  struct TE {
+    int tipCase, pNumber, qNumber, rNumber;
+    int x1Slot, x2Slot, x3Slot;
+    double qz, rz;
+  };
+  const TE *ops = (const TE *)ops_;
+  if (numOps < 1 || mxtips < 3 || !ops || !slot_out || !L_out) return -1;
+  /* inner node id mxtips+1 .. 2*mxtips-2 -> index 1 .. mxtips-2 */
+  int *slot_of = (int *)malloc(sizeof(int) * (size_t)mxtips);
+  /* at most one slot per entry */
+  unsigned char *used = (unsigned char *)calloc((size_t)numOps, 1);
+  if (!slot_of || !used) {
+    free(slot_of);
+    free(used);
+    return -1;
+  }
+  for (int i = 0; i < mxtips; i++) slot_of[i] = -1;
+  int L = 0, rc = 0;
+  for (int k = 0; k < numOps && rc == 0; k++) {
+    const TE *t = &ops[k];
+    const int inner[2] = {t->tipCase == 2 ? t->qNumber : 0,
+                          t->tipCase >= 1 ? t->rNumber : 0};
+    const int tip[2] = {t->tipCase <= 1 ? t->qNumber : 1,
+                        t->tipCase == 0 ? t->rNumber : 1};
+    if (t->tipCase < 0 || t->tipCase > 2 || t->pNumber <= mxtips ||
+        t->pNumber > 2 * mxtips - 2 || tip[0] < 1 || tip[0] > mxtips ||
+        tip[1] < 1 || tip[1] > mxtips) {
+      rc = -1;
+      break;
+    }
+    for (int o = 0; o < 2; o++) {
+      if (!inner[o]) continue;
+      const int idx = inner[o] - mxtips;
+      if (idx < 1 || idx > mxtips - 2 || slot_of[idx] < 0) {
+        rc = -1;
+        break;
+      }
+      used[slot_of[idx]] = 0;
+      slot_of[idx] = -1;
+    }
+    if (rc) break;
+    if (slot_of[t->pNumber - mxtips] >= 0) {
+      rc = -1;
+      break;
+    }
+    int s = 0;
+    while (used[s]) s++; /* s <= k: fewer than k+1 results are live */
+    used[s] = 1;
+    slot_of[t->pNumber - mxtips] = s;
+    slot_out[k] = s;
+    if (s + 1 > L) L = s + 1;
+  }
+  free(slot_of);
+  free(used);
+  if (rc == 0) *L_out = L;
+  return rc;
 }

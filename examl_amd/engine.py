@@ -369,6 +369,80 @@ class DnaCatEngine(DnaGammaEngine):
         v = self.d_out2.cpu()
         return float(v[0]), float(v[1])
 
+    # -- optRateCatPthreads (optimizeModel.c:1798) ----------------------------
+
+    def rate_scan(self, entries, p, q, z, patrat, lower_spacing,
+                  upper_spacing, max_k=None, lds_budget=-1):
+        """The per-site rate search over the last full traversal (entries
+        without the root entry; root branch p--q of length z, p a tip): one
+        kernel, one lane per site.  Reads only tips and weights, never the
+        CLV pool.  max_k caps each of the two scans (None: no cap; 0: only
+        evaluate at patrat).  lds_budget is for tests and measurements:
+        bytes of LDS the per-lane slots may take (-1: the default, 0: global
+        scratch).  Returns (patrat, lhs) as numpy arrays, or None when the
+        host loop has to serve: p is no tip, 20 states, or the kernel is
+        switched off."""
+        dev_out = self.rate_scan_launch(entries, p, q, z, patrat,
+                                        lower_spacing, upper_spacing, max_k,
+                                        lds_budget)
+        if dev_out is None:
+            return None
+        return dev_out[0].cpu().numpy(), dev_out[1].cpu().numpy()
+
+    def rate_scan_launch(self, entries, p, q, z, patrat, lower_spacing,
+                         upper_spacing, max_k=None, lds_budget=-1):
+        """rate_scan without the readback: returns the engine's own device
+        tensors (patrat, lhs), valid until the next call, or None."""
+        if self.states != 4 or not 1 <= p <= self.ntips or not entries:
+            return None
+        L_ = lib()
+        n_ops = len(entries)
+        arr = (TravEntry * n_ops)(*entries)
+        slots = (ctypes.c_int * n_ops)()
+        n_slots = ctypes.c_int(0)
+        if L_.examl_host_rate_scan_plan(
+                ctypes.cast(arr, ctypes.c_void_p), n_ops, self.ntips, slots,
+                ctypes.byref(n_slots)) != 0:
+            raise ValueError("rate_scan: entries are no post-order traversal")
+        dev = self.device
+        # scratch: allocated on first use and kept (grown if a later tree
+        # needs more)
+        tbytes = L_.examl_hip_rate_scan_table_bytes(n_ops)
+        sbytes = L_.examl_hip_rate_scan_scratch_bytes(
+            n_slots.value, ctypes.c_long(self.width), lds_budget)
+        rs = getattr(self, "_rs", None)
+        if rs is None:
+            rs = self._rs = {
+                "patrat": torch.empty(self.width, dtype=torch.float64,
+                                      device=dev),
+                "lhs": torch.empty(self.width, dtype=torch.float64,
+                                   device=dev),
+                "table": torch.empty(0, dtype=torch.uint8, device=dev),
+                "scratch": torch.empty(0, dtype=torch.uint8, device=dev)}
+        if rs["table"].numel() < tbytes:
+            rs["table"] = torch.empty(2 * tbytes, dtype=torch.uint8,
+                                      device=dev)
+        if rs["scratch"].numel() < sbytes:
+            rs["scratch"] = torch.empty(sbytes, dtype=torch.uint8, device=dev)
+        rs["patrat"].copy_(torch.from_numpy(
+            np.ascontiguousarray(patrat, dtype=np.float64)))
+        m = self.model
+        check(L_.examl_hip_rate_scan_dna_cat(
+            ctypes.cast(arr, ctypes.c_void_p), n_ops, self.ntips, int(p),
+            int(q), ctypes.c_double(z), _np_vp(m.EIGN), _np_vp(m.EI),
+            _np_vp(m.EV), _np_vp(m.tipVector), _vp(self.d_tips),
+            ctypes.c_long(self.width), _vp(self.d_wgt),
+            ctypes.c_long(self.width), ctypes.c_double(lower_spacing),
+            ctypes.c_double(upper_spacing),
+            2 ** 31 - 1 if max_k is None else int(max_k), int(lds_budget),
+            _vp(rs["patrat"]), _vp(rs["lhs"]), _vp(rs["table"]),
+            ctypes.c_long(rs["table"].numel()), _vp(rs["scratch"]),
+            ctypes.c_long(rs["scratch"].numel()), self._stream()),
+            "rate_scan")
+        if L_.examl_hip_rate_kernel_launches() == 0:
+            return None
+        return rs["patrat"], rs["lhs"]
+
 
 class Lg4Engine(DnaGammaEngine):
     """LG4M/LG4X variant: per-gamma-category matrices (EV4/tipVector4

@@ -81,6 +81,9 @@ class TreeSearch:
             self.cat_patrat = [np.ones(e.width) for e in engines]
             self.cat_lhs = [np.zeros(e.width) for e in engines]
         self._last_full = None
+        # which path the last optimize_rate_categories took for its per-site
+        # scan: "kernel" (every partition on the GPU) or "host"
+        self.rate_opt_path = None
         # fused multi-partition executors (mseg): one launch per
         # (traversal level x tipCase) over ALL partitions — used when
         # every engine is the plain dense GAMMA engine of one states
@@ -1163,6 +1166,69 @@ class TreeSearch:
             eng.host_tips.ctypes.data_as(ctypes.c_void_p),
             ctypes.c_long(eng.width), ctypes.c_int(self.tree.ntips))
 
+    def _rate_scan_kernel(self, m, lower_spacing, upper_spacing):
+        """optRateCatPthreads (optimizeModel.c:1798) for partition m as one
+        kernel launch (DnaCatEngine.rate_scan) over the entries and root
+        branch _evaluate_partial would pick; writes cat_patrat/cat_lhs in
+        place.  False: the host loop has to serve (an engine without the
+        kernel or not on a GPU, 20 states, root not at a tip, switch
+        off)."""
+        eng = self.engines[m]
+        if (not hasattr(eng, "rate_scan") or eng.model.states != 4
+                or getattr(eng, "device", None) is None
+                or eng.device.type != "cuda"):
+            return False
+        entries, p, q, zv = self._last_full
+        src = entries if self.NB == 1 \
+            else self._per_partition_entries(entries, m)
+        z = float(zv[m]) if self.NB > 1 else float(zv[0])
+        res = eng.rate_scan(src, p, q, z, self.cat_patrat[m], lower_spacing,
+                            upper_spacing)
+        if res is None:
+            return False
+        self.cat_patrat[m][:], self.cat_lhs[m][:] = res
+        return True
+
+    def _rate_scan_host(self, m, lower_spacing, upper_spacing):
+        """optRateCatPthreads (optimizeModel.c:1798) for partition m on the
+        host: one evaluatePartialGeneric call per site and candidate rate."""
+        eps = 0.00001
+        eng = self.engines[m]
+        patrat = self.cat_patrat[m]
+        lhs = self.cat_lhs[m]
+        for i in range(eng.width):
+            r0 = patrat[i]
+            l0 = self._evaluate_partial(m, i, r0)
+            left_lh = right_lh = l0
+            left_rate = right_rate = r0
+            k = 1
+            while True:
+                if not (r0 - k * lower_spacing > 0.0001):
+                    break
+                v = self._evaluate_partial(m, i, r0 - k * lower_spacing)
+                if not (v > left_lh and abs(left_lh - v) > eps):
+                    break
+                left_lh = v
+                left_rate = r0 - k * lower_spacing
+                k += 1
+            k = 1
+            while True:
+                v = self._evaluate_partial(m, i, r0 + k * upper_spacing)
+                if not (v > right_lh and abs(right_lh - v) > eps):
+                    break
+                right_lh = v
+                right_rate = r0 + k * upper_spacing
+                k += 1
+            if right_lh > l0 or left_lh > l0:
+                if right_lh > left_lh:
+                    patrat[i] = right_rate
+                    lhs[i] = right_lh
+                else:
+                    patrat[i] = left_rate
+                    lhs[i] = left_lh
+            else:
+                lhs[i] = l0
+
     def optimize_rate_categories(self, max_categories, log=None):
         """optimizeRateCategories (optimizeModel.c:2403): per-site rate
         search (optRateCatPthreads :1798), clustering
@@ -1186,42 +1252,11 @@ class TreeSearch:
                    self.engines[m].cptr.copy(),
                    self.engines[m].num_cats) for m in range(self.M)]
 
-        eps = 0.00001
-        for m, eng in enumerate(self.engines):
-            patrat = self.cat_patrat[m]
-            lhs = self.cat_lhs[m]
-            for i in range(eng.width):
-                r0 = patrat[i]
-                l0 = self._evaluate_partial(m, i, r0)
-                left_lh = right_lh = l0
-                left_rate = right_rate = r0
-                k = 1
-                while True:
-                    if not (r0 - k * lower_spacing > 0.0001):
-                        break
-                    v = self._evaluate_partial(m, i, r0 - k * lower_spacing)
-                    if not (v > left_lh and abs(left_lh - v) > eps):
-                        break
-                    left_lh = v
-                    left_rate = r0 - k * lower_spacing
-                    k += 1
-                k = 1
-                while True:
-                    v = self._evaluate_partial(m, i, r0 + k * upper_spacing)
-                    if not (v > right_lh and abs(right_lh - v) > eps):
-                        break
-                    right_lh = v
-                    right_rate = r0 + k * upper_spacing
-                    k += 1
-                if right_lh > l0 or left_lh > l0:
-                    if right_lh > left_lh:
-                        patrat[i] = right_rate
-                        lhs[i] = right_lh
-                    else:
-                        patrat[i] = left_rate
-                        lhs[i] = left_lh
-                else:
-                    lhs[i] = l0
+        self.rate_opt_path = "kernel"
+        for m in range(self.M):
+            if not self._rate_scan_kernel(m, lower_spacing, upper_spacing):
+                self.rate_opt_path = "host"
+                self._rate_scan_host(m, lower_spacing, upper_spacing)
 
         # categorizeTheRates (:2171) per partition
         for m, eng in enumerate(self.engines):

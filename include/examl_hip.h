@@ -261,9 +261,8 @@ int examl_hip_core_root_dna_gamma(long n, const double *dev_sum,
  *   sum      — sumCAT (examl/makenewzGenericSpecial.c:1850)
  *   core     — coreGTRCAT (examl/makenewzGenericSpecial.c:2402)
  * P blocks are numCats*32 doubles (left|right); diag numCats*4; the core
- * dtable scratch is numCats*4 + 8 + numCats doubles.  The CAT traversal
- * executor and the optimizeRateCategories/evaluatePartialGeneric host loop
- * are scheduled for round 2.
+ * dtable scratch is numCats*4 + 8 + numCats doubles.  The per-site rate
+ * search of optimizeRateCategories is examl_hip_rate_scan_dna_cat below.
  * ------------------------------------------------------------------------ */
 
 void examl_host_core_dtables_dna_cat(const double *EIGN, const double *rptr,
@@ -305,7 +304,7 @@ int examl_hip_core_root_dna_cat(long n, const double *dev_sum,
 
 /* CAT executors (the newviewIterative/evaluateIterative/makenewzIterative
  * CAT bodies; dev_pbuf >= numOps*numCats*32 doubles, dev_diag >= numCats*4).
- * The optimizeRateCategories/evaluatePartialGeneric host loop is round-2. */
+ */
 int examl_hip_newview_traversal_dna_cat(
     const examl_hip_trav_entry *ops, int numOps, const double *EIGN,
     const double *EI, const double *perSiteRates, int numCats,
@@ -353,6 +352,60 @@ double examl_host_evaluate_partial_dna_cat(
     double root_z, long site, double ki, int w, const double *EIGN,
     const double *EI, const double *EV, const double *tipVector,
     const unsigned char *tips, long tipStrideBytes, int mxtips);
+
+/* Slot planner of the rate-scan kernel: plain host code, no GPU call.
+ * Replaces the lVector of evaluatePartialGeneric
+ * (examl/evaluatePartialGenericSpecial.c:259, one 4-double vector per inner
+ * node) by the slots that are live at once.  ops as above (post-order, root
+ * entry excluded).  slot_out[k] is the slot entry k writes; an entry's inner
+ * operands give their slots back before its result takes the lowest free
+ * one, so a result may reuse an operand's slot.  *L_out = number of slots =
+ * the most results live at once.  Returns 0, or -1 for a list that is no
+ * post-order walk (inner operand not produced or consumed twice, ids out of
+ * range). */
+int examl_host_rate_scan_plan(const void *ops, int numOps, int mxtips,
+                              int *slot_out, int *L_out);
+
+/* replaces the per-site loop of optRateCatPthreads
+ * (examl/optimizeModel.c:1798) and the evaluatePartialGeneric calls inside
+ * it (examl/evaluatePartialGenericSpecial.c:259) for one DNA partition: one
+ * kernel, one lane per site, each lane running its site's whole scan from
+ * dev_patrat[i] downwards by lower_spacing and upwards by upper_spacing
+ * (at most max_k steps each way; max_k = 0 evaluates at the given rates
+ * only, lhs[i] = the weighted site lnL).  Leaves the chosen rates in
+ * dev_patrat and their lnL in dev_lhs (n doubles each, device).
+ * rootTipNumber must be a tip (tr->start) and rootQNumber the inner node the
+ * list ends in.  One pinned upload carries the model constants and the
+ * entry table (slots, hoisted log branch lengths) to dev_table
+ * (>= examl_hip_rate_scan_table_bytes(numOps)).  The per-lane CLV slots
+ * live in LDS while L * 32 B * 64 lanes <= ldsBudgetBytes (< 0: the
+ * default budget; 0: never), else in dev_scratch
+ * (>= examl_hip_rate_scan_scratch_bytes(L, n, ldsBudgetBytes), which is 0
+ * for the LDS home and never depends on n beyond
+ * examl_hip_rate_scan_lanes() resident lanes).  Does nothing but reset the
+ * launch counter while examl_hip_use_rate_kernel(0) is in force. */
+int examl_hip_rate_scan_dna_cat(
+    const examl_hip_trav_entry *ops, int numOps, int mxtips,
+    int rootTipNumber, int rootQNumber, double root_z, const double *EIGN,
+    const double *EI, const double *EV, const double *tipVector,
+    const unsigned char *dev_tips, long tipStrideBytes, const int *dev_wgt,
+    long n, double lower_spacing, double upper_spacing, int max_k,
+    int ldsBudgetBytes, double *dev_patrat, double *dev_lhs, void *dev_table,
+    long tableBytes, void *dev_scratch, long scratchBytes, void *stream);
+long examl_hip_rate_scan_table_bytes(int numOps);
+long examl_hip_rate_scan_scratch_bytes(int L, long n, int ldsBudgetBytes);
+int examl_hip_rate_scan_lanes(void);
+
+/* Switch for the kernel above (on by default); off sends
+ * optimizeRateCategories (examl/optimizeModel.c:2403) back to the host loop
+ * over examl_host_evaluate_partial_dna_cat.
+ * examl_hip_rate_kernel_launches: kernels the calling thread's last
+ * examl_hip_rate_scan_dna_cat call launched (1, or 0 with the switch off);
+ * examl_hip_rate_scan_slot_home: where that launch kept its slots, 0 = LDS,
+ * 1 = global scratch. */
+void examl_hip_use_rate_kernel(int on);
+int examl_hip_rate_kernel_launches(void);
+int examl_hip_rate_scan_slot_home(void);
 
 /* ---------------------------------------------------------------------------
  * Protein (20-state) GTRGAMMA surface — span 80, tip codes 1..22.  Each

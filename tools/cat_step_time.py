@@ -23,6 +23,13 @@ timer around the make_p loop of the last step
 (examl_hip_multi_cat_host_p_ms; null on a build without it) and upload_ms
 the time of one pinned copy of one step's P bytes, made and synchronised
 here.
+--rate-opt times the per-site rate search of optimize_rate_categories alone
+(no categorisation, none of the full evaluations around it), from all rates
+1.0 at the first round's spacing: --rate-kernel 1 the GPU kernel (host clock
+around upload, launch and readback, plus HIP events around the rate
+upload and the launch;
+--rate-lds B passes an LDS budget in bytes, 0 = global slots), --rate-kernel
+0 the host loop.  rate_digest sums the chosen rates for comparing the two.
 Prints ONE JSON line; lnl is printed with repr() precision so two builds
 can be compared digit for digit.  The time is a host clock around K steps
 that end in a device synchronise.
@@ -164,6 +171,56 @@ def partitioned(args):
     }), flush=True)
 
 
+def rate_opt(args):
+    assert torch.cuda.is_available(), "cat_step_time needs a GPU"
+    from examl_amd.search import TreeSearch
+    tips, wgt = make_alignment(args.taxa, args.sites, seed=42)
+    model = ea.DnaGtrModel([0.28, 0.22, 0.24, 0.26],
+                           [1.2, 2.9, 0.7, 1.0, 3.2, 1.0], alpha=0.6)
+    tree = ea.PhyloTree.random(args.taxa, seed=7, rng_z=True)
+    eng = ea.DnaCatEngine(tips, wgt, model,
+                          np.zeros(args.sites, dtype=np.int32),
+                          np.array([1.0]), device="cuda:0")
+    ts = TreeSearch(tree, [eng], rate_het="CAT")
+    ts.evaluate_generic(full=True)
+    entries, p, q, zv = ts._last_full
+    ms, ev_ms = [], []
+    for it in range(args.warmup + args.steps):
+        ts.cat_patrat[0][:] = 1.0
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if args.rate_kernel:
+            e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in "01")
+            e0.record()
+            res = eng.rate_scan_launch(entries, p, q, float(zv[0]),
+                                       ts.cat_patrat[0], 0.5, 1.0,
+                                       lds_budget=args.rate_lds)
+            e1.record()
+            ts.cat_patrat[0][:], ts.cat_lhs[0][:] = \
+                (r.cpu().numpy() for r in res)
+            e1.synchronize()
+            ev_ms.append(e0.elapsed_time(e1))
+        else:
+            ts._rate_scan_host(0, 0.5, 1.0)
+        ms.append((time.perf_counter() - t0) * 1e3)
+    ms, ev_ms = ms[args.warmup:], ev_ms[args.warmup:]
+    print(json.dumps({
+        "metric": "DNA PSR per-site rate scan",
+        "rate_kernel": args.rate_kernel,
+        "ms_median": float(np.median(ms)), "ms_min": min(ms),
+        "ms_max": max(ms),
+        "launch_ms_median": float(np.median(ev_ms)) if ev_ms else None,
+        "launch_ms_min": min(ev_ms) if ev_ms else None,
+        "launch_ms_max": max(ev_ms) if ev_ms else None,
+        "slot_home": (ea.lib().examl_hip_rate_scan_slot_home()
+                      if args.rate_kernel else None),
+        "steps": args.steps, "warmup": args.warmup, "taxa": args.taxa,
+        "sites": args.sites,
+        "rate_digest": repr(float(ts.cat_patrat[0].sum())),
+        "lhs_sum": repr(float(ts.cat_lhs[0].sum())),
+    }), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=60)
@@ -175,7 +232,12 @@ def main():
     ap.add_argument("--partitions", type=int, default=1)
     ap.add_argument("--entries", type=int, default=0)
     ap.add_argument("--makenewz", type=int, default=0)
+    ap.add_argument("--rate-opt", action="store_true")
+    ap.add_argument("--rate-kernel", type=int, choices=(0, 1), default=1)
+    ap.add_argument("--rate-lds", type=int, default=-1)
     args = ap.parse_args()
+    if args.rate_opt:
+        return rate_opt(args)
     if args.partitions > 1:
         return partitioned(args)
 
