@@ -178,6 +178,13 @@ def _bind(lib):
     lib.examl_hip_rate_scan_scratch_bytes.argtypes = [i, l, i]
     lib.examl_hip_rate_scan_scratch_bytes.restype = l
     lib.examl_hip_rate_scan_lanes.argtypes = []
+    lib.examl_hip_rate_scan_prot_cat.argtypes = \
+        lib.examl_hip_rate_scan_dna_cat.argtypes
+    lib.examl_hip_rate_scan_prot_table_bytes.argtypes = [i]
+    lib.examl_hip_rate_scan_prot_table_bytes.restype = l
+    lib.examl_hip_rate_scan_prot_scratch_bytes.argtypes = [i, l, i]
+    lib.examl_hip_rate_scan_prot_scratch_bytes.restype = l
+    lib.examl_hip_rate_scan_prot_sites.argtypes = []
     lib.examl_hip_use_rate_kernel.argtypes = [i]
     lib.examl_hip_rate_kernel_launches.argtypes = []
     lib.examl_hip_rate_scan_slot_home.argtypes = []

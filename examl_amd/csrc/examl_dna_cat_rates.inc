@@ -236,6 +236,57 @@ struct RsStage {
 };
 static thread_local RsStage g_rs_stage = {nullptr, 0, nullptr, false};
 
+/* the staging buffer, idle and with room for `need` bytes */
+static int rs_stage_acquire(size_t need, void **buf) {
+  RsStage &st = g_rs_stage;
+  if (!st.ev) CHK(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
+  if (st.busy) CHK(hipEventSynchronize(st.ev));
+  st.busy = false;
+  if (need > st.cap) {
+    if (st.buf) CHK(hipHostFree(st.buf));
+    st.buf = nullptr;
+    st.cap = 0;
+    CHK(hipHostMalloc(&st.buf, 2 * need));
+    st.cap = 2 * need;
+  }
+  *buf = st.buf;
+  return 0;
+}
+
+static int rs_stage_upload(void *dev_table, size_t need, hipStream_t s) {
+  RsStage &st = g_rs_stage;
+  CHK(hipMemcpyAsync(dev_table, st.buf, need, hipMemcpyHostToDevice, s));
+  CHK(hipEventRecord(st.ev, s));
+  st.busy = true;
+  return 0;
+}
+
+/* the entry table as the kernels read it; returns the slot of the root's q,
+ * the one result nobody consumed, or -1 */
+static int rs_fill_ops(const examl_hip_trav_entry *ops, int numOps,
+                       int mxtips, int rootQNumber, const int *slot,
+                       RsOp *t) {
+  std::vector<int> slot_of_node((size_t)(2 * mxtips), -1);
+  for (int k = 0; k < numOps; k++) {
+    const examl_hip_trav_entry &e = ops[k];
+    /* tips are read by node id (row of dev_tips); inner operands by the
+     * slot of the entry that produced them — the planner has checked that
+     * one did and that the ids are in range */
+    t[k].tc = e.tipCase;
+    t[k].a = e.tipCase != EXAML_INNER_INNER
+                 ? e.qNumber : slot_of_node[(size_t)e.qNumber];
+    t[k].b = e.tipCase == EXAML_TIP_TIP
+                 ? e.rNumber : slot_of_node[(size_t)e.rNumber];
+    t[k].dst = slot[k];
+    t[k].lq = (e.qz > ZMIN) ? log(e.qz) : log(ZMIN);
+    t[k].lr = (e.rz > ZMIN) ? log(e.rz) : log(ZMIN);
+    slot_of_node[(size_t)e.pNumber] = slot[k];
+  }
+  if (rootQNumber > mxtips && rootQNumber <= 2 * mxtips - 2)
+    return slot_of_node[(size_t)rootQNumber];
+  return -1;
+}
+
 extern "C" int examl_hip_rate_scan_dna_cat(
     const examl_hip_trav_entry *ops, int numOps, int mxtips,
     int rootTipNumber, int rootQNumber, double root_z, const double *EIGN,
@@ -261,47 +312,18 @@ extern "C" int examl_hip_rate_scan_dna_cat(
       scratchBytes < examl_hip_rate_scan_scratch_bytes(L, n, ldsBudgetBytes))
     return set_err(hipErrorInvalidValue, "rate_scan: buffer sizes");
 
-  RsStage &st = g_rs_stage;
-  if (!st.ev) CHK(hipEventCreateWithFlags(&st.ev, hipEventDisableTiming));
-  if (st.busy) CHK(hipEventSynchronize(st.ev));
-  st.busy = false;
-  if (need > st.cap) {
-    if (st.buf) CHK(hipHostFree(st.buf));
-    st.buf = nullptr;
-    st.cap = 0;
-    CHK(hipHostMalloc(&st.buf, 2 * need));
-    st.cap = 2 * need;
-  }
-  double *c = (double *)st.buf;
+  void *buf = nullptr;
+  if (int rc = rs_stage_acquire(need, &buf)) return rc;
+  double *c = (double *)buf;
   memcpy(c, EIGN, 4 * 8);
   memcpy(c + 4, EI, 16 * 8);
   memcpy(c + 20, EV, 16 * 8);
   memcpy(c + 36, tipVector, 64 * 8);
-  RsOp *t = (RsOp *)(c + RS_CONST_DOUBLES);
-  std::vector<int> slot_of_node((size_t)(2 * mxtips), -1);
-  for (int k = 0; k < numOps; k++) {
-    const examl_hip_trav_entry &e = ops[k];
-    /* tips are read by node id (row of dev_tips); inner operands by the
-     * slot of the entry that produced them — the planner has checked that
-     * one did and that the ids are in range */
-    t[k].tc = e.tipCase;
-    t[k].a = e.tipCase != EXAML_INNER_INNER
-                 ? e.qNumber : slot_of_node[(size_t)e.qNumber];
-    t[k].b = e.tipCase == EXAML_TIP_TIP
-                 ? e.rNumber : slot_of_node[(size_t)e.rNumber];
-    t[k].dst = slot[(size_t)k];
-    t[k].lq = (e.qz > ZMIN) ? log(e.qz) : log(ZMIN);
-    t[k].lr = (e.rz > ZMIN) ? log(e.rz) : log(ZMIN);
-    slot_of_node[(size_t)e.pNumber] = slot[(size_t)k];
-  }
-  /* the root's q is the one result nobody consumed */
-  if (rootQNumber > mxtips && rootQNumber <= 2 * mxtips - 2)
-    rootSlot = slot_of_node[(size_t)rootQNumber];
+  rootSlot = rs_fill_ops(ops, numOps, mxtips, rootQNumber, slot.data(),
+                         (RsOp *)(c + RS_CONST_DOUBLES));
   if (rootSlot < 0)
     return set_err(hipErrorInvalidValue, "rate_scan: root q not in the list");
-  CHK(hipMemcpyAsync(dev_table, st.buf, need, hipMemcpyHostToDevice, s));
-  CHK(hipEventRecord(st.ev, s));
-  st.busy = true;
+  if (int rc = rs_stage_upload(dev_table, need, s)) return rc;
 
   RsArgs A;
   A.consts = (const double *)dev_table;

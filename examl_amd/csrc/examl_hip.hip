@@ -5880,6 +5880,7 @@ extern "C" int examl_hip_newview_traversal_multi(
 /* the -m PSR per-site rate search: one lane per site, the whole scan on the
  * GPU (kernel, launcher and the examl_hip_rate_* entry points) */
 #include "examl_dna_cat_rates.inc"
+#include "examl_prot_cat_rates.inc"
 
 extern "C" int examl_hip_evaluate_root_multi(
     void *vh, int rootTipCase, int pNumber, int qNumber, int x1Slot,

@@ -378,9 +378,11 @@ class DnaCatEngine(DnaGammaEngine):
         kernel, one lane per site.  Reads only tips and weights, never the
         CLV pool.  max_k caps each of the two scans (None: no cap; 0: only
         evaluate at patrat).  lds_budget is for tests and measurements:
-        bytes of LDS the per-lane slots may take (-1: the default, 0: global
-        scratch).  Returns (patrat, lhs) as numpy arrays, or None when the
-        host loop has to serve: p is no tip, 20 states, or the kernel is
+        bytes of LDS the per-site slots may take (-1: the default, 0: global
+        scratch).  4 states take k_rate_scan_dna_cat (one lane per site), 20
+        states k_rate_scan_prot_cat (four lanes per site); ProtCatEngine
+        shares both methods.  Returns (patrat, lhs) as numpy arrays, or None
+        when the host loop has to serve: p is no tip, or the kernel is
         switched off."""
         dev_out = self.rate_scan_launch(entries, p, q, z, patrat,
                                         lower_spacing, upper_spacing, max_k,
@@ -393,9 +395,19 @@ class DnaCatEngine(DnaGammaEngine):
                          upper_spacing, max_k=None, lds_budget=-1):
         """rate_scan without the readback: returns the engine's own device
         tensors (patrat, lhs), valid until the next call, or None."""
-        if self.states != 4 or not 1 <= p <= self.ntips or not entries:
+        if not 1 <= p <= self.ntips or not entries:
             return None
         L_ = lib()
+        if self.states == 4:
+            scan, table_bytes, scratch_bytes = (
+                L_.examl_hip_rate_scan_dna_cat,
+                L_.examl_hip_rate_scan_table_bytes,
+                L_.examl_hip_rate_scan_scratch_bytes)
+        else:
+            scan, table_bytes, scratch_bytes = (
+                L_.examl_hip_rate_scan_prot_cat,
+                L_.examl_hip_rate_scan_prot_table_bytes,
+                L_.examl_hip_rate_scan_prot_scratch_bytes)
         n_ops = len(entries)
         arr = (TravEntry * n_ops)(*entries)
         slots = (ctypes.c_int * n_ops)()
@@ -407,8 +419,8 @@ class DnaCatEngine(DnaGammaEngine):
         dev = self.device
         # scratch: allocated on first use and kept (grown if a later tree
         # needs more)
-        tbytes = L_.examl_hip_rate_scan_table_bytes(n_ops)
-        sbytes = L_.examl_hip_rate_scan_scratch_bytes(
+        tbytes = table_bytes(n_ops)
+        sbytes = scratch_bytes(
             n_slots.value, ctypes.c_long(self.width), lds_budget)
         rs = getattr(self, "_rs", None)
         if rs is None:
@@ -427,7 +439,7 @@ class DnaCatEngine(DnaGammaEngine):
         rs["patrat"].copy_(torch.from_numpy(
             np.ascontiguousarray(patrat, dtype=np.float64)))
         m = self.model
-        check(L_.examl_hip_rate_scan_dna_cat(
+        check(scan(
             ctypes.cast(arr, ctypes.c_void_p), n_ops, self.ntips, int(p),
             int(q), ctypes.c_double(z), _np_vp(m.EIGN), _np_vp(m.EI),
             _np_vp(m.EV), _np_vp(m.tipVector), _vp(self.d_tips),
@@ -824,6 +836,11 @@ class ProtCatEngine(DnaGammaEngine):
             _vp(self.d_partials), _vp(self.d_out2), self._stream()),
             "core_root_prot_cat")
         return self.d_out2
+
+    # optRateCatPthreads (optimizeModel.c:1798): the 20-state branch of
+    # DnaCatEngine's methods
+    rate_scan = DnaCatEngine.rate_scan
+    rate_scan_launch = DnaCatEngine.rate_scan_launch
 
 
 class MultiEngine:

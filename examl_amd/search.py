@@ -1168,13 +1168,13 @@ class TreeSearch:
 
     def _rate_scan_kernel(self, m, lower_spacing, upper_spacing):
         """optRateCatPthreads (optimizeModel.c:1798) for partition m as one
-        kernel launch (DnaCatEngine.rate_scan) over the entries and root
-        branch _evaluate_partial would pick; writes cat_patrat/cat_lhs in
-        place.  False: the host loop has to serve (an engine without the
-        kernel or not on a GPU, 20 states, root not at a tip, switch
+        kernel launch (DnaCatEngine / ProtCatEngine.rate_scan) over the
+        entries and root branch _evaluate_partial would pick; writes
+        cat_patrat/cat_lhs in place.  False: the host loop has to serve (an
+        engine without the kernel or not on a GPU, root not at a tip, switch
         off)."""
         eng = self.engines[m]
-        if (not hasattr(eng, "rate_scan") or eng.model.states != 4
+        if (not hasattr(eng, "rate_scan")
                 or getattr(eng, "device", None) is None
                 or eng.device.type != "cuda"):
             return False

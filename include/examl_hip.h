@@ -396,11 +396,39 @@ long examl_hip_rate_scan_table_bytes(int numOps);
 long examl_hip_rate_scan_scratch_bytes(int L, long n, int ldsBudgetBytes);
 int examl_hip_rate_scan_lanes(void);
 
-/* Switch for the kernel above (on by default); off sends
+/* the same for one protein (20-state) partition: replaces the per-site loop
+ * of optRateCatPthreads (examl/optimizeModel.c:1798) and the
+ * evaluatePartialGeneric calls inside it (computeVectorGTRCATPROT /
+ * evaluatePartialGTRCATPROT, examl/evaluatePartialGenericSpecial.c:493/618).
+ * Arguments as for examl_hip_rate_scan_dna_cat; EIGN (20), EI (400), EV
+ * (400) and tipVector (23 x 20) are the arrays
+ * examl_host_evaluate_partial_prot_cat takes.  One kernel, four lanes per
+ * site (five states each), 64 sites per block.  The per-site CLV slots
+ * (160 B each) live in LDS while L * 160 B * 64 sites <= ldsBudgetBytes
+ * (< 0: the default budget; 0: never; capped so that a block stays within
+ * 64 KiB), else in dev_scratch
+ * (>= examl_hip_rate_scan_prot_scratch_bytes(L, n, ldsBudgetBytes), sized by
+ * at most examl_hip_rate_scan_prot_sites() resident sites).  dev_table holds
+ * >= examl_hip_rate_scan_prot_table_bytes(numOps). */
+int examl_hip_rate_scan_prot_cat(
+    const examl_hip_trav_entry *ops, int numOps, int mxtips,
+    int rootTipNumber, int rootQNumber, double root_z, const double *EIGN,
+    const double *EI, const double *EV, const double *tipVector,
+    const unsigned char *dev_tips, long tipStrideBytes, const int *dev_wgt,
+    long n, double lower_spacing, double upper_spacing, int max_k,
+    int ldsBudgetBytes, double *dev_patrat, double *dev_lhs, void *dev_table,
+    long tableBytes, void *dev_scratch, long scratchBytes, void *stream);
+long examl_hip_rate_scan_prot_table_bytes(int numOps);
+long examl_hip_rate_scan_prot_scratch_bytes(int L, long n,
+                                            int ldsBudgetBytes);
+int examl_hip_rate_scan_prot_sites(void);
+
+/* Switch for the two kernels above (on by default); off sends
  * optimizeRateCategories (examl/optimizeModel.c:2403) back to the host loop
- * over examl_host_evaluate_partial_dna_cat.
+ * over examl_host_evaluate_partial_dna_cat / _prot_cat.
  * examl_hip_rate_kernel_launches: kernels the calling thread's last
- * examl_hip_rate_scan_dna_cat call launched (1, or 0 with the switch off);
+ * examl_hip_rate_scan_dna_cat / _prot_cat call launched (1, or 0 with the
+ * switch off);
  * examl_hip_rate_scan_slot_home: where that launch kept its slots, 0 = LDS,
  * 1 = global scratch. */
 void examl_hip_use_rate_kernel(int on);

@@ -30,6 +30,8 @@ around upload, launch and readback, plus HIP events around the rate
 upload and the launch;
 --rate-lds B passes an LDS budget in bytes, 0 = global slots), --rate-kernel
 0 the host loop.  rate_digest sums the chosen rates for comparing the two.
+--protein (with --rate-opt) scans an amino-acid alignment under WAG (from
+examl_amd/data/aa_models.npz) with a ProtCatEngine instead.
 Prints ONE JSON line; lnl is printed with repr() precision so two builds
 can be compared digit for digit.  The time is a host clock around K steps
 that end in a device synchronise.
@@ -48,7 +50,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 import examl_amd as ea  # noqa: E402
-from examl_amd.synthetic import make_alignment  # noqa: E402
+from examl_amd.synthetic import make_alignment, make_alignment_aa  # noqa: E402
 
 # traffic model of DESIGN §7g, bytes per site: II 32+32 in, 32 out, 4 cptr
 ENTRY_BYTES = {ea.TIP_TIP: 38, ea.TIP_INNER: 69, ea.INNER_INNER: 100}
@@ -174,13 +176,20 @@ def partitioned(args):
 def rate_opt(args):
     assert torch.cuda.is_available(), "cat_step_time needs a GPU"
     from examl_amd.search import TreeSearch
-    tips, wgt = make_alignment(args.taxa, args.sites, seed=42)
-    model = ea.DnaGtrModel([0.28, 0.22, 0.24, 0.26],
-                           [1.2, 2.9, 0.7, 1.0, 3.2, 1.0], alpha=0.6)
+    if args.protein:
+        aa = np.load(os.path.join(os.path.dirname(ea.__file__), "data",
+                                  "aa_models.npz"))
+        tips, wgt = make_alignment_aa(args.taxa, args.sites, seed=42)
+        model = ea.ProtGtrModel(aa["frequencies"][4], aa["rates190"][4], 1.0)
+        cls = ea.ProtCatEngine
+    else:
+        tips, wgt = make_alignment(args.taxa, args.sites, seed=42)
+        model = ea.DnaGtrModel([0.28, 0.22, 0.24, 0.26],
+                               [1.2, 2.9, 0.7, 1.0, 3.2, 1.0], alpha=0.6)
+        cls = ea.DnaCatEngine
     tree = ea.PhyloTree.random(args.taxa, seed=7, rng_z=True)
-    eng = ea.DnaCatEngine(tips, wgt, model,
-                          np.zeros(args.sites, dtype=np.int32),
-                          np.array([1.0]), device="cuda:0")
+    eng = cls(tips, wgt, model, np.zeros(args.sites, dtype=np.int32),
+              np.array([1.0]), device="cuda:0")
     ts = TreeSearch(tree, [eng], rate_het="CAT")
     ts.evaluate_generic(full=True)
     entries, p, q, zv = ts._last_full
@@ -205,7 +214,8 @@ def rate_opt(args):
         ms.append((time.perf_counter() - t0) * 1e3)
     ms, ev_ms = ms[args.warmup:], ev_ms[args.warmup:]
     print(json.dumps({
-        "metric": "DNA PSR per-site rate scan",
+        "metric": ("protein" if args.protein else "DNA")
+        + " PSR per-site rate scan",
         "rate_kernel": args.rate_kernel,
         "ms_median": float(np.median(ms)), "ms_min": min(ms),
         "ms_max": max(ms),
@@ -235,6 +245,7 @@ def main():
     ap.add_argument("--rate-opt", action="store_true")
     ap.add_argument("--rate-kernel", type=int, choices=(0, 1), default=1)
     ap.add_argument("--rate-lds", type=int, default=-1)
+    ap.add_argument("--protein", action="store_true")
     args = ap.parse_args()
     if args.rate_opt:
         return rate_opt(args)
