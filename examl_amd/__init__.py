@@ -161,6 +161,9 @@ def _bind(lib):
         [p, i, p, p, p, i, p, p, p, p, l, p, l, p, l, p, p, p, p]
     lib.examl_hip_cat_fused_tile_sites.argtypes = []
     lib.examl_hip_cat_fused_launches.argtypes = []
+    lib.examl_hip_prot_cat_fused_tile_sites.argtypes = []
+    lib.examl_hip_prot_cat_fused_depth.argtypes = []
+    lib.examl_hip_prot_cat_fused_launches.argtypes = []
     lib.examl_hip_evaluate_root_dna_cat_x.argtypes = \
         [i, i, i, i, i, i, d, p, p, i, p, p, p, l, p, l, p, l, p, p, p, p, p]
     lib.examl_hip_sum_root_dna_cat.argtypes = \

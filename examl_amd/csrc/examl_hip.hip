@@ -4312,6 +4312,14 @@ extern "C" void examl_host_core_dtables_prot_cat(const double *EIGN,
                                                  int numCats, double lz,
                                                  double *dtab);
 
+/* the on-chip kernel's glue (examl_prot_cat_fused.inc, included below the
+ * rate kernels, whose quad helpers it shares) */
+static int prot_cat_fused_depth(void);
+static void launch_prot_cat_fused(const FusedProg &pg, const TravCall &c,
+                                  int numCats);
+/* on-chip launches of this thread's last protein CAT traversal call */
+static thread_local int g_prot_cat_fused_launches = 0;
+
 extern "C" int examl_hip_newview_traversal_prot_cat(
     const examl_hip_trav_entry *ops, int numOps, const double *EIGN,
     const double *EI, const double *perSiteRates, int numCats,
@@ -4319,6 +4327,7 @@ extern "C" int examl_hip_newview_traversal_prot_cat(
     double *dev_clv, long clvStride, const unsigned char *dev_tips,
     long tipStride, const int *dev_wgt, long n, unsigned int *dev_scalers,
     unsigned int *dev_inc, double *dev_pbuf, void *stream) {
+  g_prot_cat_fused_launches = 0;
   if (numOps <= 0 || n <= 0) return 0;
   if (numCats > MAX_CAT) {
     snprintf(g_err, sizeof(g_err), "traversal_prot_cat: numCats %d > %d",
@@ -4332,10 +4341,35 @@ extern "C" int examl_hip_newview_traversal_prot_cat(
                       dev_cptr, dev_clv, clvStride, dev_tips, tipStride,
                       dev_wgt, n, dev_scalers, dev_inc, dev_pbuf,
                       (hipStream_t)stream};
+  /* as examl_hip_newview_traversal_dna_cat: runs of >= 2 entries the
+   * planner accepts go through the on-chip kernel; single-entry launches,
+   * rejected lists, HIP-event profiling and examl_hip_use_fused(0) keep the
+   * per-entry kernel.  Planned once per call and before the graph shell, so
+   * the launch count is right on a replay too (list and switch are in the
+   * graph key). */
+  std::vector<FusedPlanOp> plan;
+  std::vector<int> fused_len((size_t)numOps, 0);
+  if (g_use_fused && !g_prof_on &&
+      fused_plan(ops, numOps, prot_cat_fused_depth(), FUSED_MAX_OPS, plan) > 0)
+    for (int i = 0, len; i < numOps; i += len) {
+      len = 1;
+      while (i + len < numOps &&
+             plan[(size_t)(i + len)].launch == plan[(size_t)i].launch)
+        len++;
+      fused_len[(size_t)i] = len;
+      if (len >= 2) g_prot_cat_fused_launches++;
+    }
   const int grid = grid_for(n);
   return run_traversal(
       c, host_make_p(perSiteRates, EI, EIGN, numCats, 20),
       [&](int e, const TravOperands &o) {
+        const int len = fused_len[(size_t)e];
+        if (len >= 2) {
+          FusedProg pg;
+          fused_build_prog(ops, plan, e, len, &pg);
+          launch_prot_cat_fused(pg, c, numCats);
+          return len;
+        }
         with_tip_case(ops[e].tipCase, [&](auto tc) {
           hipLaunchKernelGGL((k_newview_prot_cat<decltype(tc)::value>),
                              dim3(grid), dim3(NV_BLOCK), 0, c.stream, dev_EV,
@@ -5881,6 +5915,10 @@ extern "C" int examl_hip_newview_traversal_multi(
  * GPU (kernel, launcher and the examl_hip_rate_* entry points) */
 #include "examl_dna_cat_rates.inc"
 #include "examl_prot_cat_rates.inc"
+
+/* on-chip protein PSR (CAT) traversal: four lanes per site, category-ordered
+ * tiles (kernel, launcher and the examl_hip_prot_cat_fused_* accessors) */
+#include "examl_prot_cat_fused.inc"
 
 extern "C" int examl_hip_evaluate_root_multi(
     void *vh, int rootTipCase, int pNumber, int qNumber, int x1Slot,

@@ -780,6 +780,25 @@ int examl_hip_newview_traversal_prot_cat(
     double *dev_clv, long clvStride, const unsigned char *dev_tips,
     long tipStride, const int *dev_wgt, long n, unsigned int *dev_scalers,
     unsigned int *dev_inc, double *dev_pbuf, void *stream);
+
+/* On-chip protein CAT traversal.  Like the DNA CAT executor, the one above
+ * hands runs of at least 2 entries to one kernel that keeps each child CLV
+ * on chip for its parent (same planner, same examl_hip_use_fused switch,
+ * same exceptions; bit-identical CLVs and scaler counts).  Four lanes work
+ * on one site, and each tile's sites are taken in category order.
+ * examl_hip_prot_cat_fused_tile_sites: sites of one tile of that kernel; a
+ * launch uses at most examl_hip_fused_grid_cap() blocks, which stride over
+ * tiles.
+ * examl_hip_prot_cat_fused_depth: operand-stack slots of that kernel, the
+ * depth its lists are planned with (examl_hip_fused_plan's maxDepth).
+ * examl_hip_prot_cat_fused_launches: on-chip launches of the calling
+ * thread's last examl_hip_newview_traversal_prot_cat call, graph replays
+ * included; 0 when the per-entry kernels ran.  examl_hip_cat_fused_launches
+ * counts DNA calls only. */
+int examl_hip_prot_cat_fused_tile_sites(void);
+int examl_hip_prot_cat_fused_depth(void);
+int examl_hip_prot_cat_fused_launches(void);
+
 int examl_hip_evaluate_root_prot_cat(
     int rootTipCase, int pNumber, int qNumber, int x1Slot, int x2Slot,
     int tipSlot, double z, const double *EIGN, const double *perSiteRates,

@@ -31,7 +31,9 @@ upload and the launch;
 --rate-lds B passes an LDS budget in bytes, 0 = global slots), --rate-kernel
 0 the host loop.  rate_digest sums the chosen rates for comparing the two.
 --protein (with --rate-opt) scans an amino-acid alignment under WAG (from
-examl_amd/data/aa_models.npz) with a ProtCatEngine instead.
+examl_amd/data/aa_models.npz) with a ProtCatEngine instead.  --protein alone
+times ProtCatEngine.full_lnl on such an alignment, as the DNA step above,
+and reports examl_hip_prot_cat_fused_launches.
 Prints ONE JSON line; lnl is printed with repr() precision so two builds
 can be compared digit for digit.  The time is a host clock around K steps
 that end in a device synchronise.
@@ -173,14 +175,18 @@ def partitioned(args):
     }), flush=True)
 
 
+def wag_model():
+    aa = np.load(os.path.join(os.path.dirname(ea.__file__), "data",
+                              "aa_models.npz"))
+    return ea.ProtGtrModel(aa["frequencies"][4], aa["rates190"][4], 1.0)
+
+
 def rate_opt(args):
     assert torch.cuda.is_available(), "cat_step_time needs a GPU"
     from examl_amd.search import TreeSearch
     if args.protein:
-        aa = np.load(os.path.join(os.path.dirname(ea.__file__), "data",
-                                  "aa_models.npz"))
         tips, wgt = make_alignment_aa(args.taxa, args.sites, seed=42)
-        model = ea.ProtGtrModel(aa["frequencies"][4], aa["rates190"][4], 1.0)
+        model = wag_model()
         cls = ea.ProtCatEngine
     else:
         tips, wgt = make_alignment(args.taxa, args.sites, seed=42)
@@ -254,15 +260,21 @@ def main():
 
     assert torch.cuda.is_available(), "cat_step_time needs a GPU"
     L = ea.lib()
-    tips, wgt = make_alignment(args.taxa, args.sites, seed=42)
-    model = ea.DnaGtrModel([0.28, 0.22, 0.24, 0.26],
-                           [1.2, 2.9, 0.7, 1.0, 3.2, 1.0], alpha=0.6)
+    if args.protein:
+        tips, wgt = make_alignment_aa(args.taxa, args.sites, seed=42)
+        model, cls = wag_model(), ea.ProtCatEngine
+        counter = "examl_hip_prot_cat_fused_launches"
+    else:
+        tips, wgt = make_alignment(args.taxa, args.sites, seed=42)
+        model = ea.DnaGtrModel([0.28, 0.22, 0.24, 0.26],
+                               [1.2, 2.9, 0.7, 1.0, 3.2, 1.0], alpha=0.6)
+        cls, counter = ea.DnaCatEngine, "examl_hip_cat_fused_launches"
     rates = np.linspace(0.05, 4.0, args.cats)
     cptr = (np.arange(args.sites) % args.cats).astype(np.int32)
     np.random.default_rng(1).shuffle(cptr)
     tree = ea.PhyloTree.random(args.taxa, seed=7)
     entries, _ = tree.full_traversal()
-    eng = ea.DnaCatEngine(tips, wgt, model, cptr, rates, device="cuda:0")
+    eng = cls(tips, wgt, model, cptr, rates, device="cuda:0")
 
     L.examl_hip_use_fused(args.fused)
     try:
@@ -278,13 +290,22 @@ def main():
         L.examl_hip_use_fused(1)
 
     # a build from before the on-chip CAT kernel has no launch counter
-    count = getattr(L, "examl_hip_cat_fused_launches", None)
+    count = getattr(L, counter, None)
     launches = count() if count else 0
+    ms = elapsed / args.steps * 1e3
+    if args.protein:
+        print(json.dumps({
+            "metric": "protein PSR full_lnl step time",
+            "ms_per_step": ms, "steps": args.steps, "warmup": args.warmup,
+            "fused": args.fused, "on_chip_launches": launches,
+            "taxa": args.taxa, "sites": args.sites, "cats": args.cats,
+            "entries": len(entries), "lnl": repr(float(lnl.item())),
+        }), flush=True)
+        return
     per_entry = sum(ENTRY_BYTES[e.tipCase] for e in entries)
     ntip_reads = sum((e.tipCase != ea.INNER_INNER) + (e.tipCase == ea.TIP_TIP)
                      for e in entries)
     on_chip = 32 * len(entries) + ntip_reads + 4
-    ms = elapsed / args.steps * 1e3
     model_bytes = (on_chip if launches else per_entry) * args.sites
     print(json.dumps({
         "metric": "DNA PSR full_lnl step time",
