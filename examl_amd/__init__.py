@@ -164,6 +164,10 @@ def _bind(lib):
     lib.examl_hip_prot_cat_fused_tile_sites.argtypes = []
     lib.examl_hip_prot_cat_fused_depth.argtypes = []
     lib.examl_hip_prot_cat_fused_launches.argtypes = []
+    lib.examl_hip_prot_gamma_fused_tile_sites.argtypes = []
+    lib.examl_hip_prot_gamma_fused_depth.argtypes = []
+    lib.examl_hip_prot_gamma_fused_grid_cap.argtypes = []
+    lib.examl_hip_prot_gamma_fused_launches.argtypes = []
     lib.examl_hip_evaluate_root_dna_cat_x.argtypes = \
         [i, i, i, i, i, i, d, p, p, i, p, p, p, l, p, l, p, l, p, p, p, p, p]
     lib.examl_hip_sum_root_dna_cat.argtypes = \

@@ -3126,6 +3126,13 @@ extern "C" int examl_hip_core_prot_gamma(long n, const double *sum,
   return 0;
 }
 
+/* on-chip launches of this thread's last protein GAMMA traversal call */
+static thread_local int g_prot_gamma_fused_launches = 0;
+
+/* the on-chip protein GAMMA traversal: table kernel, fused kernel, launcher,
+ * table scratch and the examl_hip_prot_gamma_fused_* accessors */
+#include "examl_prot_gamma_fused.inc"
+
 extern "C" int examl_hip_newview_traversal_prot_gamma(
     const examl_hip_trav_entry *ops, int numOps, const double *EIGN,
     const double *EI, const double *gammaRates, const double *dev_EV,
@@ -3133,15 +3140,51 @@ extern "C" int examl_hip_newview_traversal_prot_gamma(
     const unsigned char *dev_tips, long tipStride, const int *dev_wgt, long n,
     unsigned int *dev_scalers, unsigned int *dev_inc, double *dev_pbuf,
     void *stream) {
+  g_prot_gamma_fused_launches = 0;
   if (numOps <= 0 || n <= 0) return 0;
   (void)hipGetLastError();
   const TravCall c = {"traversal_prot_gamma", 20, 3200, ops, numOps, dev_EV,
                       dev_tipVec, nullptr, dev_clv, clvStride, dev_tips,
                       tipStride, dev_wgt, n, dev_scalers, dev_inc, dev_pbuf,
                       (hipStream_t)stream};
+  /* as examl_hip_newview_traversal_prot_cat: runs of >= 2 entries the
+   * planner accepts go through the on-chip kernel; single-entry launches,
+   * rejected lists, HIP-event profiling and examl_hip_use_fused(0) keep the
+   * per-entry kernel.  Planned once per call and before the graph shell
+   * (list, switch and g_fast_math are in the graph key); the table scratch
+   * is found or grown there too, never inside a capture. */
+  std::vector<FusedPlanOp> plan;
+  std::vector<int> fused_len((size_t)numOps, 0);
+  double *tab = nullptr;
+  if (g_use_fused && !g_prof_on &&
+      fused_plan(ops, numOps, prot_gamma_fused_depth(), FUSED_MAX_OPS, plan) >
+          0)
+    for (int i = 0, len; i < numOps; i += len) {
+      len = 1;
+      while (i + len < numOps &&
+             plan[(size_t)(i + len)].launch == plan[(size_t)i].launch)
+        len++;
+      fused_len[(size_t)i] = len;
+      if (len >= 2) g_prot_gamma_fused_launches++;
+    }
+  if (g_prot_gamma_fused_launches > 0) {
+    tab = prot_gamma_tab_get(dev_pbuf, numOps);
+    if (!tab || prot_gamma_fused_grid_cap() < 1) {
+      snprintf(g_err, sizeof(g_err),
+               "traversal_prot_gamma: no table scratch or no device");
+      return -1;
+    }
+  }
   return run_traversal(
       c, host_make_p(gammaRates, EI, EIGN, 4, 20),
       [&](int e, const TravOperands &o) {
+        const int len = fused_len[(size_t)e];
+        if (len >= 2) {
+          FusedProg pg;
+          fused_build_prog(ops, plan, e, len, &pg);
+          launch_prot_gamma_fused(pg, c, tab);
+          return len;
+        }
         /* no streaming stores: see examl_hip_newview_prot_gamma */
         launch_newview_prot_gamma(ops[e].tipCase, false, c.stream, o.x1, o.x2,
                                   o.x3, o.P, dev_EV, dev_tipVec, o.t1, o.t2,

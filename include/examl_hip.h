@@ -496,6 +496,27 @@ int examl_hip_newview_traversal_prot_gamma(
     long n, unsigned int *dev_scalers, unsigned int *dev_inc,
     double *dev_pbuf, void *stream);
 
+/* On-chip protein GAMMA traversal.  The executor above hands runs of at
+ * least 2 entries to one kernel that keeps each child CLV on chip for its
+ * parent (same planner, same examl_hip_use_fused switch and exceptions as the
+ * DNA executor; CLVs and scaler counts bit-identical to the per-entry kernel
+ * under either examl_hip_fast_math setting).  A small kernel ahead of it
+ * builds each entry's P halves and tip tables once, in device scratch the
+ * library owns.  Eight lanes work on one site.
+ * examl_hip_prot_gamma_fused_tile_sites: sites of one tile of that kernel.
+ * examl_hip_prot_gamma_fused_depth: the depth its lists are planned with
+ * (examl_hip_fused_plan's maxDepth).
+ * examl_hip_prot_gamma_fused_grid_cap: blocks of one launch (resident blocks
+ * per compute unit x compute units), which stride over the tiles; 0 without
+ * a device.
+ * examl_hip_prot_gamma_fused_launches: on-chip launches of the calling
+ * thread's last examl_hip_newview_traversal_prot_gamma call, graph replays
+ * included; 0 when the per-entry kernels ran. */
+int examl_hip_prot_gamma_fused_tile_sites(void);
+int examl_hip_prot_gamma_fused_depth(void);
+int examl_hip_prot_gamma_fused_grid_cap(void);
+int examl_hip_prot_gamma_fused_launches(void);
+
 int examl_hip_evaluate_root_prot_gamma(
     int rootTipCase, int pNumber, int qNumber, int x1Slot, int x2Slot,
     int tipSlot, double z, const double *EIGN, const double *gammaRates,

@@ -33,7 +33,9 @@ upload and the launch;
 --protein (with --rate-opt) scans an amino-acid alignment under WAG (from
 examl_amd/data/aa_models.npz) with a ProtCatEngine instead.  --protein alone
 times ProtCatEngine.full_lnl on such an alignment, as the DNA step above,
-and reports examl_hip_prot_cat_fused_launches.
+and reports examl_hip_prot_cat_fused_launches.  --protein --gamma times
+DnaGammaEngine.full_lnl under WAG+GAMMA (4 rates, no categories) instead and
+reports examl_hip_prot_gamma_fused_launches.
 Prints ONE JSON line; lnl is printed with repr() precision so two builds
 can be compared digit for digit.  The time is a host clock around K steps
 that end in a device synchronise.
@@ -252,7 +254,9 @@ def main():
     ap.add_argument("--rate-kernel", type=int, choices=(0, 1), default=1)
     ap.add_argument("--rate-lds", type=int, default=-1)
     ap.add_argument("--protein", action="store_true")
+    ap.add_argument("--gamma", action="store_true")
     args = ap.parse_args()
+    assert args.protein or not args.gamma, "--gamma goes with --protein"
     if args.rate_opt:
         return rate_opt(args)
     if args.partitions > 1:
@@ -260,7 +264,11 @@ def main():
 
     assert torch.cuda.is_available(), "cat_step_time needs a GPU"
     L = ea.lib()
-    if args.protein:
+    if args.protein and args.gamma:
+        tips, wgt = make_alignment_aa(args.taxa, args.sites, seed=42)
+        model, cls = wag_model(), ea.DnaGammaEngine
+        counter = "examl_hip_prot_gamma_fused_launches"
+    elif args.protein:
         tips, wgt = make_alignment_aa(args.taxa, args.sites, seed=42)
         model, cls = wag_model(), ea.ProtCatEngine
         counter = "examl_hip_prot_cat_fused_launches"
@@ -274,7 +282,10 @@ def main():
     np.random.default_rng(1).shuffle(cptr)
     tree = ea.PhyloTree.random(args.taxa, seed=7)
     entries, _ = tree.full_traversal()
-    eng = cls(tips, wgt, model, cptr, rates, device="cuda:0")
+    if args.gamma:
+        eng = cls(tips, wgt, model, device="cuda:0")
+    else:
+        eng = cls(tips, wgt, model, cptr, rates, device="cuda:0")
 
     L.examl_hip_use_fused(args.fused)
     try:
@@ -295,7 +306,8 @@ def main():
     ms = elapsed / args.steps * 1e3
     if args.protein:
         print(json.dumps({
-            "metric": "protein PSR full_lnl step time",
+            "metric": "protein %s full_lnl step time"
+                      % ("GAMMA" if args.gamma else "PSR"),
             "ms_per_step": ms, "steps": args.steps, "warmup": args.warmup,
             "fused": args.fused, "on_chip_launches": launches,
             "taxa": args.taxa, "sites": args.sites, "cats": args.cats,
