@@ -234,6 +234,9 @@ def _bind(lib):
     lib.examl_hip_multi_use_fused.argtypes = [i]
     lib.examl_hip_multi_fused_launches.argtypes = [p]
     lib.examl_hip_multi_tile_table.argtypes = [p, i, i, p, p, i]
+    # ... of a 20-state handle: its own launch counter and grid cap
+    lib.examl_hip_multi_prot_fused_launches.argtypes = [p]
+    lib.examl_hip_multi_prot_fused_grid_cap.argtypes = []
     # on-chip multi-partition DNA PSR (CAT) traversal
     lib.examl_hip_multi_cat_create.argtypes = \
         [i, p, p, p, p, p, p, p, p, p, i, p]

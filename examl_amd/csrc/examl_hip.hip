@@ -5335,20 +5335,24 @@ struct examl_hip_multi {
   unsigned int **d_gsArr;
   char *d_callbuf; /* per-call [ESeg|SSeg|CSeg | diag | dtab | active] */
   long callbuf_bytes;
-  /* on-chip traversal (k_newview_dna_mseg_fused), DNA handles only */
+  /* on-chip traversal: k_newview_dna_mseg_fused (tiles of FUSED_SITES) on
+   * a DNA handle, k_newview_prot_gamma_mseg_fused (tiles of PGF_SITES) on a
+   * 20-state one */
   MPartDesc *d_parts;
   int *d_tilePart;
   long *d_tileSite0;
   int numTiles;
-  bool anyWide;       /* some partition streams its stores */
-  long totalSites;    /* sum of the widths */
-  int lastFused;      /* fused launches of the last traversal call */
+  bool anyWide;       /* DNA: some partition streams its stores */
+  long totalSites;    /* DNA: sum of the widths */
+  int lastFused;      /* DNA fused launches of the last traversal call */
+  double *d_protTab;  /* 20 states: entry tables of one run, [entry][part] */
+  int lastProtFused;  /* 20-state fused launches of the last traversal call */
   struct Grp {
     int tc, segOff, blkOff, grid;
   };
   struct FStep { /* one planner launch: len >= 2 -> progs[idx] through the
-                  * fused kernel, len == 1 -> singles[idx] through
-                  * k_newview_dna_mseg */
+                  * fused kernel, len == 1 -> singles[idx] through the level
+                  * kernel (k_newview_dna_mseg / k_newview_prot_mseg) */
     int len, idx;
   };
   struct Shape {
@@ -5402,9 +5406,15 @@ static bool g_multi_fused = true;
 
 extern "C" void examl_hip_multi_use_fused(int on) { g_multi_fused = on != 0; }
 
+/* k_newview_dna_mseg_fused launches only: 0 on a 20-state handle, whose
+ * on-chip launches examl_hip_multi_prot_fused_launches counts */
 extern "C" int examl_hip_multi_fused_launches(void *vh) {
   return vh ? ((examl_hip_multi *)vh)->lastFused : 0;
 }
+
+/* on-chip protein GAMMA traversal over all partitions: kernels, the
+ * handle's tile table and table scratch, launcher and accessors */
+#include "examl_prot_gamma_mseg.inc"
 
 static int msz_of(int states) { return states + states * states + 4; }
 
@@ -5543,6 +5553,9 @@ extern "C" int examl_hip_multi_create(
                      (size_t)numParts * sizeof(MPartDesc),
                      hipMemcpyHostToDevice));
     }
+  } else if (multi_prot_fused_setup(h) != 0) {
+    examl_hip_multi_destroy(h);
+    return -1;
   }
 #undef MCHK
   *out = h;
@@ -5564,6 +5577,7 @@ extern "C" void examl_hip_multi_destroy(void *vh) {
   hipFree(h->d_parts);
   hipFree(h->d_tilePart);
   hipFree(h->d_tileSite0);
+  hipFree(h->d_protTab);
   for (auto &sh : h->shapes) {
     hipFree(sh.d_segs);
     hipFree(sh.d_blk2seg);
@@ -5707,14 +5721,16 @@ static examl_hip_multi::Shape *multi_shape_get(
       if (g.grid > 0) sh.groups.push_back(g);
     }
   }
-  /* on-chip traversal (DNA): the planner's launches in entry order.  A
-   * launch of >= 2 entries is one FusedProg; a launch of one entry gets a
-   * segment group of its own behind the level groups and runs through
-   * k_newview_dna_mseg. */
+  /* on-chip traversal: the planner's launches in entry order, at the stack
+   * depth of the handle's kernel.  A launch of >= 2 entries is one
+   * FusedProg; a launch of one entry gets a segment group of its own behind
+   * the level groups and runs through the level kernel
+   * (k_newview_dna_mseg / k_newview_prot_mseg). */
   sh.fusedOk = false;
-  if (h->states == 4 && h->numTiles > 0) {
+  if (h->numTiles > 0) {
     std::vector<FusedPlanOp> plan;
-    if (fused_plan(ops, numOps, FUSED_D, FUSED_MAX_OPS, plan) > 0) {
+    if (fused_plan(ops, numOps, h->states == 4 ? FUSED_D : PGF_D,
+                   FUSED_MAX_OPS, plan) > 0) {
       for (int e = 0; e < numOps;) {
         int len = 1;
         while (e + len < numOps &&
@@ -5771,6 +5787,7 @@ extern "C" int examl_hip_newview_traversal_multi(
     const double *qzOv, const double *rzOv, void *stream) {
   examl_hip_multi *h = (examl_hip_multi *)vh;
   h->lastFused = 0;
+  h->lastProtFused = 0;
   if (numOps <= 0) return 0;
   if (numOps > h->maxOps) {
     snprintf(g_err, sizeof(g_err), "multi traversal: numOps %d > maxOps %d",
@@ -5786,13 +5803,17 @@ extern "C" int examl_hip_newview_traversal_multi(
   examl_hip_multi::Shape *shape =
       multi_shape_get(h, ops, numOps, skey, &src);
   if (!shape) return src;
-  /* DNA: the planner's launches run on chip (k_newview_dna_mseg_fused);
-   * protein handles, rejected lists, the HIP-event profiling mode and
-   * either switch off keep the level path */
-  const bool fused = S == 4 && g_multi_fused && g_use_fused && !g_prof_on &&
+  /* the planner's launches run on chip (k_newview_dna_mseg_fused, or
+   * k_newview_prot_gamma_mseg_fused on a 20-state handle); rejected lists,
+   * handles without a tile table, the HIP-event profiling mode and either
+   * switch off keep the level path */
+  const bool fused = g_multi_fused && g_use_fused && !g_prof_on &&
                      shape->fusedOk;
-  const unsigned long long key = multi_graph_key(skey, fused);
-  h->lastFused = fused ? (int)shape->progs.size() : 0;
+  /* a 20-state handle's kernels are picked by examl_hip_fast_math */
+  const unsigned long long key =
+      multi_graph_key(skey, fused) ^ (S == 20 && g_fast_math ? 0x666dULL : 0);
+  h->lastFused = fused && S == 4 ? (int)shape->progs.size() : 0;
+  h->lastProtFused = fused && S == 20 ? (int)shape->progs.size() : 0;
 
   /* pinned stage: log-z pairs, per-partition model vectors, active flags */
   HostPSlot *slot = hostP_get(h->d_stage, h->stage_doubles);
@@ -5849,7 +5870,45 @@ extern "C" int examl_hip_newview_traversal_multi(
 #define NV_MSEG(K) \
     hipLaunchKernelGGL((K), dim3(g.grid), dim3(NV_BLOCK), 0, s, dsegs, db2s, \
                        d_active)
-      if (fused) {
+      /* the level kernel of a 20-state handle over one segment group */
+      auto prot_level = [&](const examl_hip_multi::Grp &g) {
+        const MSeg *dsegs = shape->d_segs;
+        const int *db2s = shape->d_blk2seg + g.blkOff;
+        if (g_fast_math) {
+          switch (g.tc) {
+          case EXAML_TIP_TIP:
+            NV_MSEG((k_newview_prot_mseg<EXAML_TIP_TIP, true>)); break;
+          case EXAML_TIP_INNER:
+            NV_MSEG((k_newview_prot_mseg<EXAML_TIP_INNER, true>)); break;
+          default: NV_MSEG((k_newview_prot_mseg<EXAML_INNER_INNER, true>));
+          }
+        } else {
+          switch (g.tc) {
+          case EXAML_TIP_TIP:
+            NV_MSEG((k_newview_prot_mseg<EXAML_TIP_TIP, false>)); break;
+          case EXAML_TIP_INNER:
+            NV_MSEG((k_newview_prot_mseg<EXAML_TIP_INNER, false>)); break;
+          default: NV_MSEG((k_newview_prot_mseg<EXAML_INNER_INNER, false>));
+          }
+        }
+      };
+      if (fused && S == 20) {
+        /* stream order carries the dependencies between launches, and
+         * between a run's readers of the table scratch and the next run's
+         * tables kernel */
+        for (auto &st : shape->fsteps) {
+          if (st.len >= 2)
+            launch_prot_gamma_mseg_fused(h, shape->progs[(size_t)st.idx],
+                                         d_active, s);
+          else
+            prot_level(shape->singles[(size_t)st.idx]);
+          err = hipGetLastError();
+          if (err != hipSuccess) {
+            rc = set_err(err, "fused prot mseg launch");
+            break;
+          }
+        }
+      } else if (fused) {
         /* stream order carries the dependencies between launches */
         const int fgrid =
             h->numTiles < FUSED_GRID_CAP ? h->numTiles : FUSED_GRID_CAP;
@@ -5899,22 +5958,8 @@ extern "C" int examl_hip_newview_traversal_multi(
             NV_MSEG(k_newview_dna_mseg<EXAML_TIP_INNER>); break;
           default: NV_MSEG(k_newview_dna_mseg<EXAML_INNER_INNER>);
           }
-        } else if (g_fast_math) {
-          switch (g.tc) {
-          case EXAML_TIP_TIP:
-            NV_MSEG((k_newview_prot_mseg<EXAML_TIP_TIP, true>)); break;
-          case EXAML_TIP_INNER:
-            NV_MSEG((k_newview_prot_mseg<EXAML_TIP_INNER, true>)); break;
-          default: NV_MSEG((k_newview_prot_mseg<EXAML_INNER_INNER, true>));
-          }
         } else {
-          switch (g.tc) {
-          case EXAML_TIP_TIP:
-            NV_MSEG((k_newview_prot_mseg<EXAML_TIP_TIP, false>)); break;
-          case EXAML_TIP_INNER:
-            NV_MSEG((k_newview_prot_mseg<EXAML_TIP_INNER, false>)); break;
-          default: NV_MSEG((k_newview_prot_mseg<EXAML_INNER_INNER, false>));
-          }
+          prot_level(g);
         }
 #undef NV_MSEG
         err = hipGetLastError();

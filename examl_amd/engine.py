@@ -935,9 +935,16 @@ class MultiEngine:
             self._stream()), "newview_traversal_multi")
 
     def fused_launches(self):
-        """On-chip kernel launches of the last newview_traversal call (0
-        when it took the level path)."""
+        """On-chip DNA kernel launches of the last newview_traversal call (0
+        when it took the level path, and always 0 over 20-state engines:
+        prot_fused_launches counts those)."""
         return lib().examl_hip_multi_fused_launches(self.h)
+
+    def prot_fused_launches(self):
+        """On-chip protein GAMMA kernel launches of the last
+        newview_traversal call over 20-state engines (0 when it took the
+        level path)."""
+        return lib().examl_hip_multi_prot_fused_launches(self.h)
 
     def evaluate_root(self, tree, p, q, z, active=None, all_reduce=False):
         """z: scalar (joint) or per-partition sequence (-M).  Returns the

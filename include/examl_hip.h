@@ -885,16 +885,36 @@ int examl_hip_core_root_multi(
  * over the tiles of all partitions that keeps each child CLV on chip for
  * its parent, a launch of one entry runs the level kernel over that entry.
  * The P blocks, the scaler increments and the finalize are the level
- * path's, and CLVs, scalers and lnL are bit-identical to it.  The level
- * path remains for protein handles, for lists the planner rejects or cuts
- * into one-entry launches only, while profiling is enabled, and when
- * either switch is off; toggling a switch on
- * a live handle never replays the other path's cached graph. */
+ * path's, and CLVs, scalers and lnL are bit-identical to it.  A 20-state
+ * handle takes its own on-chip path under the same switches (below).  The
+ * level path remains for lists the planner rejects or cuts into one-entry
+ * launches only, while profiling is enabled, and when either switch is
+ * off; toggling a switch on a live handle never replays the other path's
+ * cached graph. */
 void examl_hip_multi_use_fused(int on);
-/* number of on-chip kernel launches the last
+/* number of on-chip DNA kernel launches the last
  * examl_hip_newview_traversal_multi call on h issued or replayed from its
- * graph; 0 when it took the level path */
+ * graph; 0 when it took the level path, and always 0 on a 20-state handle
+ * (examl_hip_multi_prot_fused_launches counts those) */
 int examl_hip_multi_fused_launches(void *h);
+/* On-chip multi-partition protein GAMMA traversal: newviewIterative's
+ * partition loop (newviewGenericSpecial.c:1064) around the 20-state GAMMA
+ * case (newviewGTRGAMMAPROT, :4600) as one kernel per planner launch of two
+ * or more entries, over tiles of examl_hip_prot_gamma_fused_tile_sites()
+ * sites from examl_hip_multi_tile_table, eight lanes on a site, planned at
+ * examl_hip_prot_gamma_fused_depth().  A small kernel ahead of it builds
+ * the P halves and tip tables of every (entry, partition) once, in scratch
+ * the handle owns; a handle whose scratch cannot be allocated keeps the
+ * level path.  CLVs, scalers and lnL are bit-identical to the level path
+ * under either examl_hip_fast_math setting.
+ * examl_hip_multi_prot_fused_launches: on-chip launches of the last
+ * examl_hip_newview_traversal_multi call on the 20-state handle h, issued
+ * or replayed from its graph; 0 when it took the level path.
+ * examl_hip_multi_prot_fused_grid_cap: blocks of one launch (resident
+ * blocks per compute unit x compute units), which stride over the tiles; 0
+ * without a device. */
+int examl_hip_multi_prot_fused_launches(void *h);
+int examl_hip_multi_prot_fused_grid_cap(void);
 /* The tile table of that kernel: plain host code, no GPU call.  Tiles never
  * straddle partitions: partition p of width w owns ceil(w / tileSites)
  * consecutive tiles (none for w == 0), in partition order.  Writes the

@@ -35,7 +35,11 @@ examl_amd/data/aa_models.npz) with a ProtCatEngine instead.  --protein alone
 times ProtCatEngine.full_lnl on such an alignment, as the DNA step above,
 and reports examl_hip_prot_cat_fused_launches.  --protein --gamma times
 DnaGammaEngine.full_lnl under WAG+GAMMA (4 rates, no categories) instead and
-reports examl_hip_prot_gamma_fused_launches.
+reports examl_hip_prot_gamma_fused_launches.  --protein --gamma --partitions
+N splits the sites equally into N partitions with an empirical model and
+alpha each and times MultiEngine (one traversal of all partitions plus the
+root evaluation); --fused then sets examl_hip_multi_use_fused, and
+on_chip_launches is MultiEngine.prot_fused_launches.
 Prints ONE JSON line; lnl is printed with repr() precision so two builds
 can be compared digit for digit.  The time is a host clock around K steps
 that end in a device synchronise.
@@ -183,6 +187,55 @@ def wag_model():
     return ea.ProtGtrModel(aa["frequencies"][4], aa["rates190"][4], 1.0)
 
 
+def partitioned_prot_gamma(args):
+    """--protein --gamma --partitions N: MultiEngine over N equal 20-state
+    GAMMA partitions with models of their own; a step is one traversal of
+    all partitions plus the root evaluation.  --fused sets
+    examl_hip_multi_use_fused."""
+    assert torch.cuda.is_available(), "cat_step_time needs a GPU"
+    L = ea.lib()
+    NP = args.partitions
+    tips, wgt = make_alignment_aa(args.taxa, args.sites, seed=42)
+    tree = ea.PhyloTree.random(args.taxa, seed=7)
+    entries, (p, q, z) = tree.full_traversal()
+    aa = np.load(os.path.join(os.path.dirname(ea.__file__), "data",
+                              "aa_models.npz"))
+    cut = np.linspace(0, args.sites, NP + 1).astype(int)
+    engs = [ea.DnaGammaEngine(
+        np.ascontiguousarray(tips[:, cut[i]:cut[i + 1]]),
+        wgt[cut[i]:cut[i + 1]],
+        ea.ProtGtrModel(aa["frequencies"][4 + i % 3], aa["rates190"][4 + i % 3],
+                        0.5 + 0.05 * i), device="cuda:0") for i in range(NP)]
+    multi = ea.MultiEngine(engs)
+
+    def step():
+        multi.newview_traversal(entries)
+        return multi.evaluate_root(tree, p, q, z)
+
+    L.examl_hip_multi_use_fused(args.fused)
+    try:
+        for _ in range(args.warmup):
+            lnl = step()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            lnl = step()
+        torch.cuda.synchronize()
+        elapsed = time.perf_counter() - t0
+    finally:
+        L.examl_hip_multi_use_fused(1)
+    # a build from before the on-chip kernel has no such counter
+    count = getattr(multi, "prot_fused_launches", None)
+    print(json.dumps({
+        "metric": "partitioned protein GAMMA step time",
+        "ms_per_step": elapsed / args.steps * 1e3, "steps": args.steps,
+        "warmup": args.warmup, "fused": args.fused,
+        "on_chip_launches": count() if count else 0, "taxa": args.taxa,
+        "sites": args.sites, "partitions": NP, "entries": len(entries),
+        "lnl": repr(float(lnl.sum().item())),
+    }), flush=True)
+
+
 def rate_opt(args):
     assert torch.cuda.is_available(), "cat_step_time needs a GPU"
     from examl_amd.search import TreeSearch
@@ -259,6 +312,8 @@ def main():
     assert args.protein or not args.gamma, "--gamma goes with --protein"
     if args.rate_opt:
         return rate_opt(args)
+    if args.partitions > 1 and args.protein and args.gamma:
+        return partitioned_prot_gamma(args)
     if args.partitions > 1:
         return partitioned(args)
 
